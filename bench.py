@@ -104,7 +104,44 @@ def parse():
     ap.add_argument("--variant-a", action="store_true",
                     help="reference-native input rate: streams at 252 kS/s, no stage 0 (SURVEY 8d Variant A; fp64-bound, "
                          "reported for completeness -- the headline workload is the default 2.016 MS/s Variant B)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed for a fixed sample of rank 0's streams as DIR/<name>.npy "
+                         "(float32/float64, at most 64 MB): the last step's fp64 cascade output and the bits decoded over the timed steps")
     return ap.parse_args()
+
+
+DUMP_BUDGET = 64 << 20          # bytes, all files of --dump-outputs together
+DUMP_MAX_STREAMS = 256
+DUMP_SEED = 20240601
+
+
+def dump_sample(S, F, steps, y3_per_frame):
+    """The streams --dump-outputs writes: a seeded sample (the same for the same --streams / --frames / --steps), as many as
+    fit the budget with their fp64 cascade output and a generous estimate of their timed bits (32 per frame and step, +1 %)."""
+    per_stream = F * y3_per_frame * 16 + (steps * F * 32 * 101 // 100 + 64) * 4
+    n = max(1, min(S, DUMP_MAX_STREAMS, DUMP_BUDGET // per_stream))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(S, n, replace=False))
+
+
+def dump_outputs(out_dir, nv, pipe, ids, bits_before):
+    """What a caller of the timed path receives, for the streams `ids` (chain 518): y3.npy [n, F * FRAME_Y3, 2] float64 --
+    the FIR cascade's 900 S/s output of the LAST timed launch, bit for bit; bits.npy [n, L] float32 -- the bits decoded over
+    the timed launches (1 = 'B', 0 = 'Y', -1 past a stream's end; when they would overrun the budget, each row keeps the
+    most recent ones); bit_counts.npy [n] float64 -- every bit the stream has decoded since the reset; stream_ids.npy."""
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    y3 = np.stack([pipe.debug_y3(int(s), 0) for s in ids])
+    timed = [pipe.bits(int(s), 0)[b:] for s, b in zip(ids, bits_before)]
+    room = max(1, (DUMP_BUDGET - 4096 - y3.nbytes - 2 * 8 * len(ids)) // (4 * len(ids)))     # 4096: the four .npy headers
+    timed = [t[-room:] for t in timed]
+    bits = np.full((len(ids), max(len(t) for t in timed)), -1.0, dtype=np.float32)
+    for k, t in enumerate(timed):
+        bits[k, :len(t)] = np.frombuffer(t.encode("ascii"), dtype=np.uint8) == ord("B")
+    np.save(out / "y3.npy", y3)
+    np.save(out / "bits.npy", bits)
+    np.save(out / "bit_counts.npy", np.array([pipe.bit_count(int(s), 0) for s in ids], dtype=np.float64))
+    np.save(out / "stream_ids.npy", ids.astype(np.float64))
+    print(f"outputs of the last timed step of {len(ids)} streams written to {out}", file=sys.stderr)
 
 
 def run_wideband(args, nv, signals, ranks, rank, world, device, place):
@@ -337,6 +374,8 @@ def run_group(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.group or args.wideband):
+        raise SystemExit("--dump-outputs writes the headline workload's outputs: not with --group or --wideband")
     if args.group:
         if args.verify == 0:
             raise SystemExit("--verify 0: an unchecked number is no number")
@@ -454,6 +493,9 @@ def main():
     for _ in range(args.warmup):
         step()
     pipe.fetch()
+    if args.dump_outputs and rank == 0:
+        dump_ids = dump_sample(S, F, args.steps, nv.FRAME_Y3)
+        dump_before = [pipe.bit_count(int(s), 0) for s in dump_ids]
     pipe.enable_timing(True)
     pipe.kernel_time_stats(0, reset=True)
     pipe.wait_stats(reset=True)
@@ -470,6 +512,8 @@ def main():
     dem_ms, _ = pipe.kernel_time_stats(1)
     w_polls, w_units, w_launches = pipe.wait_stats()
     total_bits = sum(pipe.bit_count(s, 0) for s in range(0, S, max(1, S // 64)))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, nv, pipe, dump_ids, dump_before)
 
     # ---- parity AFTER the timed region: what the measured launches produced.  The handle was reset before the warm-up;
     # since then it has run the same F frames (warmup + steps) times, its filter and demodulator state carried from launch

@@ -7,6 +7,9 @@ bench.py's cpu_baseline leg -- never from the navtex_amd package.
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
+import json
+import os
 import subprocess
 import tempfile
 from pathlib import Path
@@ -17,6 +20,7 @@ import numpy as np
 ROOT = Path(__file__).resolve().parent.parent
 LIB = ROOT / "oracle" / "_build" / "libnvx_oracle.so"
 REF = ROOT / "oracle" / "_ref"
+REF_RECORD = ROOT / "tests" / "golden" / "ref_outputs.json"
 
 
 def _build():
@@ -289,6 +293,35 @@ def run_ref(seam: str, data: bytes, probe: Tuple = (), ref_dir: Path | None = No
 
 def have_ref_wav() -> bool:
     return (REF / "ref_wav").exists()
+
+
+def sha256(data) -> str:
+    """Of bytes, or of an array's contiguous bytes."""
+    return hashlib.sha256(data if isinstance(data, bytes) else np.ascontiguousarray(data).tobytes()).hexdigest()
+
+
+_records = None
+
+
+def ref_record(key: str, live, available: bool | None = None):
+    """What the compiled reference answers on one fixed test input (JSON data: bit strings, messages, traces, SHA-256 of
+    fp64 seams).  Where the seams are built (`available`, default have_ref()) live() runs them and the record committed in
+    tests/golden/ref_outputs.json must say the same; elsewhere the record stands in for them.  NVX_REF_RECORD=1 (with
+    the seams built) rewrites the record from the live answers instead:
+        NVX_REF_RECORD=1 python -m pytest tests/test_ref_live.py tests/test_deviations.py"""
+    global _records
+    if _records is None:
+        _records = json.loads(REF_RECORD.read_text()) if REF_RECORD.exists() else {}
+    if not (have_ref() if available is None else available):
+        assert key in _records, f"{REF_RECORD.name} holds no answer of the reference for {key}"
+        return _records[key]
+    got = json.loads(json.dumps(live()))
+    if os.environ.get("NVX_REF_RECORD") == "1":
+        _records[key] = got
+        REF_RECORD.write_text(json.dumps(_records, indent=1, sort_keys=True) + "\n")
+    else:
+        assert _records.get(key) == got, f"{REF_RECORD.name} is not what the compiled reference answers for {key}"
+    return got
 
 
 def ref_wav_write(frames: np.ndarray, rate: int, ref_dir: Path | None = None) -> bytes:

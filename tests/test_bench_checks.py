@@ -98,6 +98,43 @@ def test_a_leg_that_raises_fails_the_run_with_status_4(tmp_path, capsys):
     bench.finish(line, True, NoRanks(), 0, leg_errors=False)      # returns
 
 
+def test_dump_outputs_is_a_fixed_sample_in_float_within_64_mb(tmp_path):
+    """--dump-outputs: the same seeded sample of streams for the same arguments; every file float32/float64; the bits row of a
+    stream is what it decoded after the warm-up (1 = 'B'), the most recent ones when a long run would overrun the 64 MB."""
+    import bench
+
+    class StubPipe:                                  # the three calls dump_outputs makes, on made-up results
+        def __init__(self, n_bits):
+            self.n_bits = n_bits
+
+        def debug_y3(self, s, c):
+            return np.full((4 * 288, 2), s + 0.5)
+
+        def bits(self, s, c):
+            return ("BY" * self.n_bits)[s % 2:][:self.n_bits]
+
+        def bit_count(self, s, c):
+            return self.n_bits
+
+    ids = bench.dump_sample(4096, 4, 30, 288)
+    assert np.array_equal(ids, bench.dump_sample(4096, 4, 30, 288)) and len(ids) == 256 and len(set(ids)) == 256
+    assert not np.array_equal(ids, np.arange(256)) and 0 <= ids.min() and ids.max() < 4096
+    assert np.array_equal(bench.dump_sample(8, 4, 30, 288), np.arange(8))
+    bench.dump_outputs(tmp_path / "a", None, StubPipe(100), ids, [40] * len(ids))
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"y3", "bits", "bit_counts", "stream_ids"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["y3"].shape == (256, 4 * 288, 2) and np.array_equal(got["y3"][:, 0, 0], ids + 0.5)
+    assert got["bits"].shape == (256, 60) and np.array_equal(got["stream_ids"], ids) and set(got["bit_counts"]) == {100}
+    assert np.array_equal(got["bits"][0], [float(c == "B") for c in StubPipe(100).bits(int(ids[0]), 0)[40:]])
+    # a run far too long for the budget: fewer streams, each row the most recent bits, everything under 64 MB
+    ids = bench.dump_sample(4096, 4, 100000, 288)
+    bench.dump_outputs(tmp_path / "b", None, StubPipe(4 * 32 * 100000), ids, [0] * len(ids))
+    assert 1 <= len(ids) < 256 and sum(f.stat().st_size for f in (tmp_path / "b").glob("*.npy")) <= 64 << 20
+    bits = np.load(tmp_path / "b" / "bits.npy")
+    assert bits.min() >= 0 and bits[0, -1] == float(StubPipe(4 * 32 * 100000).bits(int(ids[0]), 0)[-1] == "B")
+
+
 def test_self_launch_passes_a_signal_on_to_its_ranks(tmp_path):
     """`bench.py --gpus N` killed by SIGTERM (a driver timeout that is not a process-group kill) must take the ranks
     with it: they run in a session of their own and get the signal passed on."""
@@ -144,6 +181,44 @@ def test_bench_checks_the_timed_launches_and_reports_the_seals():
     for name in ("252k", "2016k"):
         st = live["streams"][name]
         assert st["dropped"] == 0 and st["bits_equal_oracle"] and 0 < st["p50_ms"] <= st["p99_ms"] <= st["max_ms"] < 150.0, st
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_step_and_repeat_exactly(nv, oracle, tmp_path):
+    """bench.py --dump-outputs at test size, twice: the two dumps are identical, file for file; y3 is the last timed launch's
+    cascade output bit for bit and each bits row is what the stream decoded after the warm-up -- the oracle fed the stream's
+    frames warmup + steps times says so."""
+    warmup, steps, S, F = 2, 3, 64, 4
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--streams", str(S), "--frames", str(F), "--steps", str(steps),
+                              "--warmup", str(warmup), "--no-cpu", "--no-legs", "--no-stage0-extra", "--after-timed", "32", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-3000:]
+        assert _line(out)["steps"] == steps and _line(out)["parity"] is True
+        dumps.append({f.stem: np.load(f) for f in d.glob("*.npy")})
+    a, b = dumps
+    assert set(a) == set(b) == {"y3", "bits", "bit_counts", "stream_ids"}
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k].view(np.uint8), b[k].view(np.uint8)), k
+    ids = a["stream_ids"].astype(int)
+    assert len(ids) == S and a["y3"].shape == (S, F * nv.FRAME_Y3, 2)
+    n3 = F * nv.FRAME_Y3
+    for k in (0, S // 2, S - 1):
+        st, _ = signals.stream_params(nv, int(ids[k]), nv.RATE_RAW)
+        buf = nv.DeviceBuffer(F * nv.FRAME_RAW * 4)              # generated the way bench.py generates its batch
+        nv.synth_device([st], nv.RATE_RAW, F * nv.FRAME_RAW, buf, F * nv.FRAME_RAW)
+        iq = buf.download(F * nv.FRAME_RAW * 4, dtype=np.int16).reshape(-1, 2)
+        buf.free()
+        ref = oracle.Pipe(chain_mask=1, charlayer=False, tap_y3=(warmup + steps) * n3)
+        for _ in range(warmup + steps):
+            ref.push_raw(iq)
+        assert np.array_equal(a["y3"][k].view(np.uint64), ref.y3(0)[-n3:].view(np.uint64)), f"stream {ids[k]}"
+        row = a["bits"][k]
+        timed = "".join("B" if v == 1 else "Y" for v in row[row >= 0])
+        whole = ref.bits(0)
+        assert a["bit_counts"][k] == len(whole) and whole.endswith(timed) and len(timed) > steps * F * 30, f"stream {ids[k]}"
 
 
 @pytest.mark.gpu

@@ -1,7 +1,7 @@
 """Where the product deliberately does NOT behave like the reference (include/navtex_amd.h
-section A): each deviation is pinned here from BOTH sides -- what the compiled reference does (oracle/_ref, build
-container only: the `ref`-gated tests) and what the library documents and does (the GPU half is
-tests/test_gpu_deviations.py).
+section A): each deviation is pinned here from BOTH sides -- what the compiled reference does (oracle/_ref where it is
+built, else its answers recorded in tests/golden/ref_outputs.json: oracle_binding.ref_record) and what the library
+documents and does (the GPU half is tests/test_gpu_deviations.py).
 
   1. re-initialisation in mid-stream   receiver/fir1cpp.C:65-77, receiver/fir2cpp.C:90-110
   2. the input domain of sample_in_1   receiver/capt_sched.c:511 (the only caller passes int16 values)
@@ -20,12 +20,10 @@ import cases
 import oracle_binding as ob
 
 GOLD = json.loads((Path(__file__).parent / "golden" / "golden.json").read_text())
-needs_ref = pytest.mark.skipif(not ob.have_ref(), reason="compiled reference (oracle/_ref) not present")
 INT_MAX = 2 ** 31 - 1
 
 
 # ------------------------------------------------------------------------------------------ 1. re-initialisation
-@needs_ref
 @pytest.mark.parametrize("which", [1, 2, 3], ids=["init_fir_filter1", "init_fir2_wrapper", "both"])
 def test_reinit_in_mid_stream_is_a_partial_reset_in_the_reference(nv, oracle, which):
     """The reference's init functions called AGAIN in front of sample n (capt_sched.c calls each once, :552-555, :612):
@@ -40,12 +38,17 @@ def test_reinit_in_mid_stream_is_a_partial_reset_in_the_reference(nv, oracle, wh
     rec = GOLD["iq"]["two_carrier"]
     iq = cases.make_iq(nv, rec["spec"])
     n = iq.shape[0] // 2 + 1237                          # nowhere in particular: no multiple of 4, 28, 280, 2520
-    reinit = ob.run_ref("bits", iq.tobytes(), ("reinit", n, which))
+
+    def live():
+        runs = {"reinit": ob.run_ref("bits", iq.tobytes(), ("reinit", n, which)), "head": ob.run_ref("bits", iq[:n].tobytes()),
+                "fresh": ob.run_ref("bits", iq[n:].tobytes())}
+        return {k: {tag: r[tag].decode() for tag in ("bits518", "bits490")} for k, r in runs.items()}
+    ref = ob.ref_record(f"reinit/{which}", live)
+    reinit, head, fresh = ref["reinit"], ref["head"], ref["fresh"]
     p = oracle.Pipe(chain_mask=3, charlayer=False)
     p.push(iq[:n]); p.reinit(which); p.push(iq[n:])
-    head, fresh = ob.run_ref("bits", iq[:n].tobytes()), ob.run_ref("bits", iq[n:].tobytes())
     for c, tag in ((0, "bits518"), (1, "bits490")):
-        got = reinit[tag].decode()
+        got = reinit[tag]
         assert p.bits(c) == got, f"(a) {tag}"
         whole = rec[tag]                                 # the uninterrupted run (golden = compiled reference)
         m = min(len(got), len(whole)) - 1
@@ -54,14 +57,13 @@ def test_reinit_in_mid_stream_is_a_partial_reset_in_the_reference(nv, oracle, wh
         assert behind - len(fresh[tag]) >= 60, f"(b) {tag}: {behind} vs {len(fresh[tag])} of a fresh start"
 
 
-@needs_ref
 def test_once_before_the_first_sample_every_reading_is_the_same(nv, oracle):
     """... and called once, before the first sample -- all capt_sched.c ever does -- "FIR1 cleared", "FIR2-518 cleared" and
     "everything zero" are one state: the reference re-initialised in front of sample 0 is the reference."""
     rec = GOLD["iq"]["offset_490"]
     iq = cases.make_iq(nv, rec["spec"])
-    again = ob.run_ref("bits", iq.tobytes(), ("reinit", 0, 3))
-    assert again["bits518"].decode() == rec["bits518"] and again["bits490"].decode() == rec["bits490"]
+    again = ob.ref_record("reinit/at_0", lambda: {tag: ob.run_ref("bits", iq.tobytes(), ("reinit", 0, 3))[tag].decode() for tag in ("bits518", "bits490")})
+    assert again["bits518"] == rec["bits518"] and again["bits490"] == rec["bits490"]
 
 
 # ------------------------------------------------------------------------------------------ 2. input domain
@@ -118,9 +120,8 @@ def test_the_references_sample_counter_overflows_after_27_days_and_silences_it(n
     overflow_at = k0 + (INT_MAX - v)                     # the sample whose increment passes INT_MAX
     assert control.startswith(bits) and abs(len(bits) - (overflow_at // 9 - 66)) <= 3
     assert len(control) - len(bits) > 2700               # ... and 25 s of good signal decode to nothing
-    if ob.have_ref():
-        ref = ob.run_ref("dec", np.ascontiguousarray(y3).tobytes(), ("inject", k0, v))["bits518"].decode()
-        assert ref == bits, "the compiled reference and the oracle disagree about the overflow"
+    ref = ob.ref_record(f"counter_overflow/{margin}", lambda: {"bits518": ob.run_ref("dec", np.ascontiguousarray(y3).tobytes(), ("inject", k0, v))["bits518"].decode()})
+    assert ref["bits518"] == bits, "the compiled reference and the oracle disagree about the overflow"
     assert nv.lib.nvx_fsm_selftest(12345, 3_000_000) == 0
 
 

@@ -884,6 +884,11 @@ def test_two_receivers_two_capture_rings_one_handle(nv, oracle):
                 # neither radio runs more than about a frame ahead of the other (they share a sample clock)
                 while pos - min(progress) > nv.FRAME_IN:
                     time.sleep(0.0005)
+                # and, as in test_live_capture_ring_fake_sdr, never outruns its consumer: wait while its ring (504 000) is nearly full
+                while True:
+                    r, d, c = _stats(nv, caps[s])
+                    if r - d - c + m <= 480000: break
+                    time.sleep(0.0005)
                 nv.lib.nvx_capture_callback(xi[pos:pos + m].ctypes.data, xq[pos:pos + m].ctypes.data, None, m, 0, caps[s])
                 pos += m
                 progress[s] = pos

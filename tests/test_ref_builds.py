@@ -28,7 +28,7 @@ REF_SRC = Path("/root/reference/receiver")
 GOLDEN = ROOT / "tests" / "golden" / "golden.json"
 
 pytestmark = [pytest.mark.ref,
-              pytest.mark.skipif(not REF_SRC.exists() or shutil.which("g++") is None, reason="needs the reference's sources and g++ (build container only)")]
+              pytest.mark.skipif(not os.path.isdir(REF_SRC) or shutil.which("g++") is None, reason="needs the reference's sources and g++ (build container only)")]
 
 SEAMS = ("y1", "y2_518", "y2_490", "y3_518", "y3_490")
 

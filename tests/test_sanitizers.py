@@ -1,7 +1,10 @@
 """ASan + UBSan over the product's host-side C (CPU build only; GPU sanitizers are not
 available on the pool).  Inputs: every golden character-layer case, fuzz, WAV edge
 cases, generator sweeps, the SQLite sink, the demodulator FSM tables -- see tests/harness/sanitize_host.c."""
+import functools
 import json
+import platform
+import shutil
 import subprocess
 from pathlib import Path
 
@@ -9,6 +12,25 @@ import cases
 
 ROOT = Path(__file__).resolve().parent.parent
 GOLD = json.loads((Path(__file__).parent / "golden" / "golden.json").read_text())
+
+
+@functools.lru_cache(maxsize=None)
+def _fixed_layout():
+    """The command prefix that runs one program with its own address layout unrandomised (setarch -R; no system setting
+    changes).  ThreadSanitizer as GCC 11 ships it knows the layout of 28 bits of mmap randomisation; under a kernel that
+    uses more (vm.mmap_rnd_bits = 32) the program lands where it does not look and stops with "unexpected memory mapping".
+    Empty where setarch is missing or the personality change is not permitted."""
+    cmd = [shutil.which("setarch") or "/usr/bin/setarch", platform.machine(), "-R"]
+    try:
+        ok = subprocess.run(cmd + ["true"], capture_output=True, timeout=30).returncode == 0
+    except OSError:
+        ok = False
+    return cmd if ok else []
+
+
+def _run_tsan(args):
+    return subprocess.run(_fixed_layout() + [str(a) for a in args], capture_output=True, text=True, timeout=600,
+                          env={"TSAN_OPTIONS": "halt_on_error=1", "PATH": "/usr/bin:/bin"})
 
 
 def test_host_c_is_clean_under_asan_ubsan(nv, tmp_path):
@@ -37,8 +59,7 @@ def test_capture_ring_is_clean_under_tsan(tmp_path):
     subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=thread", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
                     f"-I{ROOT / 'include'}", f"-I{csrc}", str(ROOT / "tests" / "harness" / "tsan_capture.cpp"),
                     str(csrc / "nvx_capture.cpp"), "-x", "c", str(csrc / "nvx_wav.c"), "-o", str(exe), "-lpthread"], check=True)
-    out = subprocess.run([str(exe), str(tmp_path / "rec.wav")], capture_output=True, text=True, timeout=600,
-                         env={"TSAN_OPTIONS": "halt_on_error=1", "PATH": "/usr/bin:/bin"})
+    out = _run_tsan([exe, tmp_path / "rec.wav"])
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     assert "tsan capture ok" in out.stdout and "dropped 0 " not in out.stdout      # overruns really happened
 
@@ -53,8 +74,7 @@ def test_group_is_clean_under_tsan(tmp_path):
     subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=thread", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
                     f"-I{ROOT / 'include'}", f"-I{csrc}", str(ROOT / "tests" / "harness" / "tsan_group.cpp"),
                     str(csrc / "nvx_group.cpp"), "-o", str(exe), "-lpthread"], check=True)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
-                         env={"TSAN_OPTIONS": "halt_on_error=1", "PATH": "/usr/bin:/bin"})
+    out = _run_tsan([exe])
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     assert "tsan group ok" in out.stdout
 
@@ -66,7 +86,7 @@ def test_host_pool_is_clean_under_tsan(tmp_path):
     csrc = ROOT / "navtex_amd" / "csrc"
     subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=thread", f"-I{csrc}", str(ROOT / "tests" / "harness" / "tsan_pool.cpp"),
                     "-o", str(exe), "-lpthread"], check=True)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env={"TSAN_OPTIONS": "halt_on_error=1", "PATH": "/usr/bin:/bin"})
+    out = _run_tsan([exe])
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     assert "tsan pool ok" in out.stdout
 
@@ -84,6 +104,6 @@ def test_push_path_is_clean_under_tsan(tmp_path):
     subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=thread", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
                     f"-I{ROOT / 'include'}", f"-I{csrc}", str(ROOT / "tests" / "harness" / "tsan_push.cpp"),
                     str(csrc / "nvx_push.cpp"), "-x", "c", str(csrc / "nvx_wav.c"), "-o", str(exe), "-lpthread"], check=True)
-    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600, env={"TSAN_OPTIONS": "halt_on_error=1", "PATH": "/usr/bin:/bin"})
+    out = _run_tsan([exe])
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     assert "tsan push ok" in out.stdout
