@@ -79,39 +79,42 @@ extern "C" void nvx_config_default(nvx_config *c)
     c->max_frames = 1; c->char_layer = 1; c->push_mode = 0;
 }
 
+// Wait until nothing of the handle's is in flight: its last launch, which may sit on a caller's stream, then both streams.
+static int drain(nvx_handle *h)
+{
+    if (h->launch_done_valid) HIP_TRY(hipEventSynchronize(h->launch_done));
+    if (h->stream) HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->stream2) HIP_TRY(hipStreamSynchronize(h->stream2));
+    return NVX_OK;
+}
+
+// every input stream at one state-block parity and one sample count: launches need no participant list
+static inline bool streams_together(const nvx_handle *h)
+{
+    for (int s = 1; s < h->n_in; s++)
+        if (h->parity[s] != h->parity[0] || h->g0s[s] != h->g0s[0]) return false;
+    return true;
+}
+
 static void free_handle(nvx_handle *h)
 {
     if (!h) return;
-    hipSetDevice(h->cfg.device);
-    if (h->launch_done_valid) hipEventSynchronize(h->launch_done);      // the last launch may sit on a caller's stream
-    if (h->stream) hipStreamSynchronize(h->stream);
-    if (h->stream2) hipStreamSynchronize(h->stream2);
-    hipFree(h->d_whist[0]); hipFree(h->d_whist[1]);
-    hipFree(h->d_y2[0]); hipFree(h->d_y2[1]); hipFree(h->d_y2row);
-    hipFree(h->d_masks); hipFree(h->d_active); hipFree(h->d_cstate[0]); hipFree(h->d_cstate[1]); hipFree(h->d_y3[0]); hipFree(h->d_y3[1]);
-    for (int i = 0; i < 2; i++) { if (h->casc_done[i]) hipEventDestroy(h->casc_done[i]); if (h->demod_done[i]) hipEventDestroy(h->demod_done[i]); }
-    if (h->launch_done) hipEventDestroy(h->launch_done);
-    hipFree(h->d_ties); if (h->h_ties) hipHostFree(h->h_ties);
-    hipFree(h->d_dd[0]); hipFree(h->d_dd[1]); hipFree(h->d_di); hipFree(h->d_fsm_tab); hipFree(h->d_dphi); hipFree(h->d_in); hipFree(h->d_words); hipFree(h->d_ctrl);
-    if (h->h_status) hipHostFree(h->h_status);
-    for (auto &r : h->res) {
-        hipFree(r.d_bits); hipFree(r.d_nbits);
-        if (r.h_bits) hipHostFree(r.h_bits);
-        if (r.h_nbits) hipHostFree(r.h_nbits);
-        hipFree(r.d_part); if (r.h_part) hipHostFree(r.h_part);
-        if (r.copied) hipEventDestroy(r.copied);
-        if (r.done) hipEventDestroy(r.done);
-        for (int i = 0; i < 8; i++) if (r.ev[i]) hipEventDestroy(r.ev[i]);
+    const std::string err = g_err;          // a destroy reports nothing: a create that unwinds keeps its own error text
+    (void)hipSetDevice(h->cfg.device);
+    (void)drain(h);
+    snprintf(g_err, sizeof g_err, "%s", err.c_str());
+    (void)hipFree(h->d_dphi);
+    for (auto it = h->made.rbegin(); it != h->made.rend(); ++it) {      // the streams, made first, go last
+        switch (it->first) {
+        case HipRes::stream: (void)hipStreamDestroy((hipStream_t)it->second); break;
+        case HipRes::event:  (void)hipEventDestroy((hipEvent_t)it->second); break;
+        case HipRes::device: (void)hipFree(it->second); break;
+        case HipRes::pinned: (void)hipHostFree(it->second); break;
+        }
     }
-    for (int i = 0; i < 2; i++) {
-        if (h->h_stage[i]) hipHostFree(h->h_stage[i]);
-    }
-    for (auto &s : h->slots) {
+    for (auto &s : h->slots)
         if (s.sitor) nvx_sitor_free(s.sitor);
-    }
     for (auto *c : h->sinks) delete c;
-    if (h->stream) hipStreamDestroy(h->stream);
-    if (h->stream2) hipStreamDestroy(h->stream2);
     delete h;
 }
 
@@ -137,7 +140,8 @@ extern "C" int nvx_create(const nvx_config *cfg, nvx_handle **out)
     nvx_handle *h = new nvx_handle();
     h->cfg = *cfg;
     h->n_in = cfg->n_streams;
-    h->n_streams = cfg->wideband ? NVX_WB_SUBBANDS * cfg->n_streams : cfg->n_streams;
+    h->per_in = cfg->wideband ? NVX_WB_SUBBANDS : 1;
+    h->n_streams = h->per_in * cfg->n_streams;
     h->n_slots = 2 * h->n_streams;
     h->cascade_raw = cfg->raw_rate && !cfg->wideband;
     h->frame_in = (cfg->raw_rate || cfg->wideband) ? (size_t)NVX_FRAME_RAW : (size_t)NVX_FRAME_IN;
@@ -175,62 +179,64 @@ extern "C" int nvx_create(const nvx_config *cfg, nvx_handle **out)
 #define CR_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
         nvx_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); free_handle(h); \
         return e_ == hipErrorOutOfMemory ? NVX_ERR_NOMEM : NVX_ERR_HIP; } } while (0)
+    // every stream, event and buffer goes on the release list as it is made: free_handle unwinds whatever was made
+#define CR_MAKE(kind, p, expr) do { CR_TRY(expr); h->made.push_back({ HipRes::kind, (void *)(p) }); } while (0)
 
-    CR_TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    CR_TRY(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
+    CR_MAKE(stream, h->stream, hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    CR_MAKE(stream, h->stream2, hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
     for (int i = 0; i < 2; i++) {
-        CR_TRY(hipEventCreateWithFlags(&h->casc_done[i], hipEventDisableTiming));
-        CR_TRY(hipEventCreateWithFlags(&h->demod_done[i], hipEventDisableTiming));
+        CR_MAKE(event, h->casc_done[i], hipEventCreateWithFlags(&h->casc_done[i], hipEventDisableTiming));
+        CR_MAKE(event, h->demod_done[i], hipEventCreateWithFlags(&h->demod_done[i], hipEventDisableTiming));
     }
-    CR_TRY(hipEventCreateWithFlags(&h->launch_done, hipEventDisableTiming));
+    CR_MAKE(event, h->launch_done, hipEventCreateWithFlags(&h->launch_done, hipEventDisableTiming));
     std::vector<uint8_t> active(h->n_slots);
     for (int i = 0; i < h->n_slots; i++) active[i] = h->slots[i].active;
-    CR_TRY(hipMalloc(&h->d_masks, h->n_streams));
-    CR_TRY(hipMalloc(&h->d_active, h->n_slots));
+    CR_MAKE(device, h->d_masks, hipMalloc(&h->d_masks, h->n_streams));
+    CR_MAKE(device, h->d_active, hipMalloc(&h->d_active, h->n_slots));
     CR_TRY(hipMemcpy(h->d_masks, h->masks.data(), h->n_streams, hipMemcpyHostToDevice));
     CR_TRY(hipMemcpy(h->d_active, active.data(), h->n_slots, hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; i++) CR_TRY(hipMalloc(&h->d_cstate[i], (size_t)h->n_streams * NVX_CASCADE_STATE_BYTES));
-    for (int i = 0; i < 2; i++) CR_TRY(hipMalloc(&h->d_y3[i], (size_t)h->n_slots * h->y3_cap * sizeof(double2)));
+    for (int i = 0; i < 2; i++) CR_MAKE(device, h->d_cstate[i], hipMalloc(&h->d_cstate[i], (size_t)h->n_streams * NVX_CASCADE_STATE_BYTES));
+    for (int i = 0; i < 2; i++) CR_MAKE(device, h->d_y3[i], hipMalloc(&h->d_y3[i], (size_t)h->n_slots * h->y3_cap * sizeof(double2)));
     if (cfg->wideband) {
         // the fused wideband kernel's waves end at FIR2: a row of 9 kS/s fp64 pairs per ACTIVE chain, two buffers (nvx_kernels.h)
         std::vector<int> rows(h->n_slots, -1);
         for (int i = 0; i < h->n_slots; i++) if (h->slots[i].active) rows[i] = h->y2_rows++;
         h->y2_pitch = (size_t)NVX_Y2_PREFIX + (size_t)cfg->max_frames * NVX_Y2_PER_FRAME;
-        CR_TRY(hipMalloc(&h->d_y2row, (size_t)h->n_slots * sizeof(int)));
+        CR_MAKE(device, h->d_y2row, hipMalloc(&h->d_y2row, (size_t)h->n_slots * sizeof(int)));
         CR_TRY(hipMemcpy(h->d_y2row, rows.data(), (size_t)h->n_slots * sizeof(int), hipMemcpyHostToDevice));
         h->y2row = rows;
-        for (int i = 0; i < 2; i++) CR_TRY(hipMalloc(&h->d_y2[i], (size_t)h->y2_rows * h->y2_pitch * sizeof(double2)));
+        for (int i = 0; i < 2; i++) CR_MAKE(device, h->d_y2[i], hipMalloc(&h->d_y2[i], (size_t)h->y2_rows * h->y2_pitch * sizeof(double2)));
     }
-    for (int i = 0; i < 2; i++) CR_TRY(hipMalloc(&h->d_dd[i], (size_t)NVX_DEMOD_DOUBLES * h->n_slots * sizeof(double)));
-    CR_TRY(hipMalloc(&h->d_di, (size_t)NVX_DEMOD_INTS * h->n_slots * sizeof(int)));
-    CR_TRY(hipMalloc(&h->d_fsm_tab, NVX_FSM_TABLE_ALLOC * sizeof(uint32_t)));
+    for (int i = 0; i < 2; i++) CR_MAKE(device, h->d_dd[i], hipMalloc(&h->d_dd[i], (size_t)NVX_DEMOD_DOUBLES * h->n_slots * sizeof(double)));
+    CR_MAKE(device, h->d_di, hipMalloc(&h->d_di, (size_t)NVX_DEMOD_INTS * h->n_slots * sizeof(int)));
+    CR_MAKE(device, h->d_fsm_tab, hipMalloc(&h->d_fsm_tab, NVX_FSM_TABLE_ALLOC * sizeof(uint32_t)));
     CR_TRY(hipMemcpy(h->d_fsm_tab, nvx_fsm_table_host(), NVX_FSM_TABLE_ALLOC * sizeof(uint32_t), hipMemcpyHostToDevice));
-    CR_TRY(hipMalloc(&h->d_words, (size_t)(h->y3_cap / 9) * h->n_slots * sizeof(unsigned short)));
-    CR_TRY(hipMalloc(&h->d_ctrl, (size_t)(NVX_CASCADE_CTRL_INTS + h->n_streams) * sizeof(int)));
-    CR_TRY(hipMalloc(&h->d_ties, sizeof(nvx_tie_stats)));
-    CR_TRY(hipHostMalloc((void **)&h->h_ties, sizeof(nvx_tie_stats), hipHostMallocDefault));
-    CR_TRY(hipHostMalloc((void **)&h->h_status, RESULT_SLOTS * NVX_STATUS_INTS * sizeof(int), hipHostMallocDefault));
+    CR_MAKE(device, h->d_words, hipMalloc(&h->d_words, (size_t)(h->y3_cap / 9) * h->n_slots * sizeof(unsigned short)));
+    CR_MAKE(device, h->d_ctrl, hipMalloc(&h->d_ctrl, (size_t)(NVX_CASCADE_CTRL_INTS + h->n_streams) * sizeof(int)));
+    CR_MAKE(device, h->d_ties, hipMalloc(&h->d_ties, sizeof(nvx_tie_stats)));
+    CR_MAKE(pinned, h->h_ties, hipHostMalloc((void **)&h->h_ties, sizeof(nvx_tie_stats), hipHostMallocDefault));
+    CR_MAKE(pinned, h->h_status, hipHostMalloc((void **)&h->h_status, RESULT_SLOTS * NVX_STATUS_INTS * sizeof(int), hipHostMallocDefault));
     memset(h->h_status, 0, RESULT_SLOTS * NVX_STATUS_INTS * sizeof(int));
     for (auto &r : h->res) {
-        CR_TRY(hipMalloc(&r.d_bits, (size_t)h->n_slots * h->bits_cap));
-        CR_TRY(hipMalloc(&r.d_nbits, (size_t)h->n_slots * sizeof(int)));
-        CR_TRY(hipHostMalloc((void **)&r.h_bits, (size_t)h->n_slots * h->bits_cap, hipHostMallocDefault));
-        CR_TRY(hipHostMalloc((void **)&r.h_nbits, (size_t)h->n_slots * sizeof(int), hipHostMallocDefault));
-        CR_TRY(hipMalloc(&r.d_part, (size_t)h->n_in * sizeof(nvx_part)));
-        CR_TRY(hipHostMalloc((void **)&r.h_part, (size_t)h->n_in * sizeof(nvx_part), hipHostMallocDefault));
-        CR_TRY(hipEventCreateWithFlags(&r.copied, hipEventDisableTiming));
-        CR_TRY(hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
-        for (int i = 0; i < 8; i++) CR_TRY(hipEventCreate(&r.ev[i]));
+        CR_MAKE(device, r.d_bits, hipMalloc(&r.d_bits, (size_t)h->n_slots * h->bits_cap));
+        CR_MAKE(device, r.d_nbits, hipMalloc(&r.d_nbits, (size_t)h->n_slots * sizeof(int)));
+        CR_MAKE(pinned, r.h_bits, hipHostMalloc((void **)&r.h_bits, (size_t)h->n_slots * h->bits_cap, hipHostMallocDefault));
+        CR_MAKE(pinned, r.h_nbits, hipHostMalloc((void **)&r.h_nbits, (size_t)h->n_slots * sizeof(int), hipHostMallocDefault));
+        CR_MAKE(device, r.d_part, hipMalloc(&r.d_part, (size_t)h->n_in * sizeof(nvx_part)));
+        CR_MAKE(pinned, r.h_part, hipHostMalloc((void **)&r.h_part, (size_t)h->n_in * sizeof(nvx_part), hipHostMallocDefault));
+        CR_MAKE(event, r.copied, hipEventCreateWithFlags(&r.copied, hipEventDisableTiming));
+        CR_MAKE(event, r.done, hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
+        for (int i = 0; i < 8; i++) CR_MAKE(event, r.ev[i], hipEventCreate(&r.ev[i]));
     }
-    if (cfg->wideband)         // the channeliser's 40-sample halo in front of a launch, two blocks by stream parity (nvx_kernels.h)
-        for (int i = 0; i < 2; i++) CR_TRY(hipMalloc(&h->d_whist[i], (size_t)h->n_in * 40 * 4));
+    if (cfg->wideband)         // the channeliser's halo in front of a launch, two blocks by stream parity (nvx_kernels.h)
+        for (int i = 0; i < 2; i++) CR_MAKE(device, h->d_whist[i], hipMalloc(&h->d_whist[i], (size_t)h->n_in * NVX_WB_HALO * 4));
     if (cfg->push_mode) {
         h->stage_cap = (size_t)(cfg->max_frames + 1) * h->frame_in;
         for (int i = 0; i < 2; i++) {
-            CR_TRY(hipHostMalloc((void **)&h->h_stage[i], (size_t)h->n_in * h->stage_cap * 4, hipHostMallocDefault));
+            CR_MAKE(pinned, h->h_stage[i], hipHostMalloc((void **)&h->h_stage[i], (size_t)h->n_in * h->stage_cap * 4, hipHostMallocDefault));
             h->set_launch[i].assign(h->n_in, 0);
         }
-        CR_TRY(hipMalloc(&h->d_in, (size_t)h->n_in * cfg->max_frames * h->frame_in * 4));
+        CR_MAKE(device, h->d_in, hipMalloc(&h->d_in, (size_t)h->n_in * cfg->max_frames * h->frame_in * 4));
         h->fill.assign(h->n_in, 0);
         h->cur.assign(h->n_in, 0);
         h->active.assign(h->n_in, 1);
@@ -240,6 +246,7 @@ extern "C" int nvx_create(const nvx_config *cfg, nvx_handle **out)
         h->last_push_ns.assign(h->n_in, nvx_now_ns());
         h->stall_ns.assign(h->n_in, cfg->stall_timeout_ms < 0 ? 0 : (int64_t)(cfg->stall_timeout_ms ? cfg->stall_timeout_ms : 2000) * 1000000);
     }
+#undef CR_MAKE
 #undef CR_TRY
     rc = nvx_reset(h);
     if (rc != NVX_OK) { free_handle(h); return rc; }
@@ -248,6 +255,46 @@ extern "C" int nvx_create(const nvx_config *cfg, nvx_handle **out)
 }
 
 
+// Everything input streams [first, last) carry, set as a fresh handle has it (handle locked, nothing in flight).  An input
+// stream owns per_in decoded streams of two slots (chains) each; y2 rows go in slot order to the active slots only.
+static int clear_streams_locked(nvx_handle *h, int first, int last)
+{
+    const int n_in = last - first, d0 = first * h->per_in, n_d = n_in * h->per_in, slot0 = 2 * d0, n_sl = 2 * n_d;
+    for (int i = 0; i < 2; i++) {
+        HIP_TRY(hipMemsetAsync(h->d_cstate[i] + (size_t)d0 * NVX_CASCADE_STATE_BYTES, 0, (size_t)n_d * NVX_CASCADE_STATE_BYTES, h->stream));
+        HIP_TRY(hipMemsetAsync(h->d_dd[i] + (size_t)slot0 * NVX_DEMOD_DOUBLES, 0, (size_t)n_sl * NVX_DEMOD_DOUBLES * sizeof(double), h->stream));
+        if (h->d_whist[i]) HIP_TRY(hipMemsetAsync(h->d_whist[i] + (size_t)first * NVX_WB_HALO, 0, (size_t)n_in * NVX_WB_HALO * 4, h->stream));
+    }
+    // ints, field-major [NVX_DEMOD_INTS][n_slots]: all zero except prev_offset = -1 (decoder.C:30) and the bit-FSM
+    // phase = -1 (waiting); -1 is all ones
+    for (int f = 0; f < NVX_DEMOD_INTS; f++)
+        HIP_TRY(hipMemsetAsync(h->d_di + (size_t)f * h->n_slots + slot0, (f == NVX_DI_PREV_OFFSET || f == NVX_DI_PHASE) ? 0xff : 0,
+                               (size_t)n_sl * sizeof(int), h->stream));
+    // FIR3's history: silence in front of the chains' next launch (the prefix of their y2 rows, both buffers)
+    if (h->d_y2[0]) {
+        auto rows_before = [&](int slot) { return (size_t)std::count_if(h->y2row.begin(), h->y2row.begin() + slot, [](int r) { return r >= 0; }); };
+        const size_t row0 = rows_before(slot0), n_rows = rows_before(slot0 + n_sl) - row0;
+        for (int i = 0; i < 2; i++)
+            HIP_TRY(hipMemset2DAsync(h->d_y2[i] + row0 * h->y2_pitch, h->y2_pitch * sizeof(double2), 0, (size_t)NVX_Y2_PREFIX * sizeof(double2), n_rows, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    for (int k = slot0; k < slot0 + n_sl; k++) {
+        Slot &s = h->slots[k];
+        s.bits.clear(); s.base = 0; s.polled = 0;
+        if (s.sitor) nvx_sitor_reset(s.sitor);
+    }
+    const int64_t now = nvx_now_ns();
+    for (int s = first; s < last; s++) {
+        h->g0s[s] = 0; h->ended[s] = 0;
+        if (!h->fill.empty()) { h->fill[s] = 0; h->active[s] = 1; h->last_push_ns[s] = now; }
+        // what was staged is dropped: the frames of an attached capture ring and the stream's no longer line up, so its
+        // latency bookkeeping ends here (nvx_capture_latency keeps what it has; a new nvx_capture_start books again)
+        if (ArrivalClock *ac = h->arrival[s]) { std::lock_guard<std::mutex> al(ac->mu); ac->base = UINT64_MAX; }
+    }
+    return NVX_OK;
+}
+
+// The whole handle starts anew: results in flight are dropped (not collected), every stream cleared.
 extern "C" int nvx_reset(nvx_handle *h)
 {
     if (!h) return NVX_ERR_ARG;
@@ -255,55 +302,25 @@ extern "C" int nvx_reset(nvx_handle *h)
     StreamClose closing(h, lk, 0, h->n_in);              // push calls in progress end first; later ones start on the fresh streams
     StagingQuiesce quiet(h, lk);                         // no push is copying into the staging sets while they are emptied
     HIP_TRY(hipSetDevice(h->cfg.device));
-    if (h->launch_done_valid) HIP_TRY(hipEventSynchronize(h->launch_done));   // launches on a caller's stream included
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream2));
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
     h->launch_done_valid = false;
     for (auto &r : h->res) r.pending = false;
     h->collected = h->launched;
     std::fill(h->parity.begin(), h->parity.end(), (uint8_t)0);
-    std::fill(h->g0s.begin(), h->g0s.end(), 0ull);
     h->diverged = false;
-    // a reset drops whatever was staged: the frames of an attached capture ring and the handle's no longer line up, so its
-    // latency bookkeeping ends here (nvx_capture_latency keeps what it has; a new nvx_capture_start books again)
-    for (ArrivalClock *ac : h->arrival)
-        if (ac) { std::lock_guard<std::mutex> al(ac->mu); ac->base = UINT64_MAX; }
     h->demod_pending[0] = h->demod_pending[1] = false;
     h->poisoned = false; h->poison_why.clear();
-    std::fill(h->ended.begin(), h->ended.end(), (uint8_t)0);
-    for (int i = 0; i < 2 && h->d_whist[i]; i++) HIP_TRY(hipMemsetAsync(h->d_whist[i], 0, (size_t)h->n_in * 40 * 4, h->stream));
-    for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(h->d_cstate[i], 0, (size_t)h->n_streams * NVX_CASCADE_STATE_BYTES, h->stream));
-    // FIR3's history: silence in front of every chain's first launch (the prefix of every y2 row, both buffers)
-    for (int i = 0; i < 2 && h->d_y2[i]; i++)
-        HIP_TRY(hipMemset2DAsync(h->d_y2[i], h->y2_pitch * sizeof(double2), 0, (size_t)NVX_Y2_PREFIX * sizeof(double2), (size_t)h->y2_rows, h->stream));
-    for (int i = 0; i < 2; i++) HIP_TRY(hipMemsetAsync(h->d_dd[i], 0, (size_t)NVX_DEMOD_DOUBLES * h->n_slots * sizeof(double), h->stream));
-    // ints: all zero except prev_offset = -1 (decoder.C:30) and the bit-FSM phase = -1 (waiting)
-    std::vector<int> ints((size_t)NVX_DEMOD_INTS * h->n_slots, 0);
-    for (int i = 0; i < h->n_slots; i++) {
-        ints[(size_t)NVX_DI_PREV_OFFSET * h->n_slots + i] = -1;
-        ints[(size_t)NVX_DI_PHASE * h->n_slots + i] = -1;
-    }
-    HIP_TRY(hipMemcpyAsync(h->d_di, ints.data(), ints.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    const nvx_tie_stats ties0 = { 0, 0, 0x7f800000u, 0 };
+    static const nvx_tie_stats ties0 = { 0, 0, 0x7f800000u, 0 };
     *h->h_ties = ties0;
     HIP_TRY(hipMemcpyAsync(h->d_ties, &ties0, sizeof ties0, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (auto &s : h->slots) { s.bits.clear(); s.base = 0; s.polled = 0; if (s.sitor) nvx_sitor_reset(s.sitor); }
-    if (!h->fill.empty()) {
-        std::fill(h->fill.begin(), h->fill.end(), (size_t)0);
-        std::fill(h->active.begin(), h->active.end(), (uint8_t)1);
-        std::fill(h->last_push_ns.begin(), h->last_push_ns.end(), nvx_now_ns());
-        // (every copy out of the staging sets has finished: the streams were synchronised above)
-        for (int i = 0; i < 2; i++) std::fill(h->set_launch[i].begin(), h->set_launch[i].end(), (uint64_t)0);
-    }
-    return NVX_OK;
+    // (every copy out of the staging sets has finished: the streams were drained above)
+    for (int i = 0; i < 2; i++) std::fill(h->set_launch[i].begin(), h->set_launch[i].end(), (uint64_t)0);
+    return clear_streams_locked(h, 0, h->n_in);
 }
 
-// One stream starts anew (header: nvx_stream_reset): what nvx_reset does, for the rows of ONE input stream -- the cascade
-// state blocks, the demodulator state, FIR3's history and the channeliser halo of a wideband handle, the character layers,
-// the bit history, the staging -- while the other streams keep everything they carry.  The handle's work is taken in
-// first (the stream's rows must be out of every kernel's reach); afterwards the streams are on different clocks, so
-// launches carry participant lists until they meet again.
+// One stream starts anew (header: nvx_stream_reset): what nvx_reset does, for ONE input stream, while the other streams
+// keep everything they carry.  The handle's work is taken in first (the stream's rows must be out of every kernel's
+// reach); afterwards the streams are on different clocks, so launches carry participant lists until they meet again.
 extern "C" int nvx_stream_reset(nvx_handle *h, int stream)
 {
     if (!h || stream < 0 || stream >= h->n_in) { nvx_set_error("nvx_stream_reset: bad stream"); return NVX_ERR_ARG; }
@@ -314,37 +331,9 @@ extern "C" int nvx_stream_reset(nvx_handle *h, int stream)
     StagingQuiesce quiet(h, lk);
     HIP_TRY(hipSetDevice(h->cfg.device));
     { int rc = nvx_collect_locked(h); if (rc != NVX_OK) return rc; }   // bits and messages of everything launched so far are delivered
-    if (h->launch_done_valid) HIP_TRY(hipEventSynchronize(h->launch_done));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream2));
-    const int per = h->cfg.wideband ? NVX_WB_SUBBANDS : 1;             // decoded streams of this input stream
-    const int d0 = per * stream, slot0 = 2 * d0, n_sl = 2 * per;
-    for (int i = 0; i < 2; i++) {
-        HIP_TRY(hipMemsetAsync(h->d_cstate[i] + (size_t)d0 * NVX_CASCADE_STATE_BYTES, 0, (size_t)per * NVX_CASCADE_STATE_BYTES, h->stream));
-        HIP_TRY(hipMemsetAsync(h->d_dd[i] + (size_t)slot0 * NVX_DEMOD_DOUBLES, 0, (size_t)n_sl * NVX_DEMOD_DOUBLES * sizeof(double), h->stream));
-        if (h->d_whist[i]) HIP_TRY(hipMemsetAsync(h->d_whist[i] + (size_t)stream * 40, 0, 40 * 4, h->stream));
-        for (int k = 0; k < n_sl && h->d_y2[i]; k++)
-            if (h->y2row[slot0 + k] >= 0)
-                HIP_TRY(hipMemsetAsync(h->d_y2[i] + (size_t)h->y2row[slot0 + k] * h->y2_pitch, 0, (size_t)NVX_Y2_PREFIX * sizeof(double2), h->stream));
-    }
-    // ints: all zero except prev_offset = -1 (decoder.C:30) and the bit-FSM phase = -1 (waiting), as nvx_reset
-    std::vector<int> zero(n_sl, 0), minus(n_sl, -1);
-    for (int f = 0; f < NVX_DEMOD_INTS; f++) {
-        const int *src = (f == NVX_DI_PREV_OFFSET || f == NVX_DI_PHASE) ? minus.data() : zero.data();
-        HIP_TRY(hipMemcpyAsync(h->d_di + (size_t)f * h->n_slots + slot0, src, (size_t)n_sl * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    for (int k = 0; k < n_sl; k++) {
-        Slot &s = h->slots[slot0 + k];
-        s.bits.clear(); s.base = 0; s.polled = 0;
-        if (s.sitor) nvx_sitor_reset(s.sitor);
-    }
-    h->g0s[stream] = 0; h->ended[stream] = 0;
-    if (!h->fill.empty()) { h->fill[stream] = 0; h->active[stream] = 1; h->last_push_ns[stream] = nvx_now_ns(); }
-    if (ArrivalClock *ac = h->arrival[stream]) { std::lock_guard<std::mutex> al(ac->mu); ac->base = UINT64_MAX; }
-    bool together = true;
-    for (int s = 1; s < h->n_in && together; s++) together = h->parity[s] == h->parity[0] && h->g0s[s] == h->g0s[0];
-    h->diverged = !together;
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
+    { int rc = clear_streams_locked(h, stream, stream + 1); if (rc != NVX_OK) return rc; }
+    h->diverged = !streams_together(h);
     return NVX_OK;
 }
 
@@ -392,7 +381,6 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     // sample count and the kernels need no list.  From the first partial launch on (a stream of a push-mode handle had
     // no frame) the streams are on their own clocks: the launch carries a list with each participant's parity and g0.
     // A launch that ends streams carries one too (their true sample counts).
-    const int per_part = h->cfg.wideband ? NVX_WB_SUBBANDS : 1;          // decoded streams per input stream
     const int n3_full = n_frames * NVX_FRAME_Y3;
     const bool with_list = h->diverged || part != nullptr || tail_n3 != nullptr;
     r.n_part = 0;
@@ -416,7 +404,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     nvx_demod_args da{};
     da.y3 = h->d_y3[yb]; da.y3_cap = (size_t)h->y3_cap; da.y3_base = 0; da.n3 = n3_full;
     da.n_slots = h->n_slots; da.slot_active = h->d_active;
-    da.g0 = h->g0s[0]; da.part = d_list; da.n_part = r.n_part; da.per_part = per_part;
+    da.g0 = h->g0s[0]; da.part = d_list; da.n_part = r.n_part; da.per_part = h->per_in;
     da.dstate[0] = h->d_dd[p0]; da.dstate[1] = h->d_dd[p0 ^ 1];     // (read, write) without a list; [0], [1] with one
     da.state_i = h->d_di; da.fsm_table = h->d_fsm_tab; da.words = h->d_words;
     da.bits = r.d_bits; da.bits_cap = h->bits_cap; da.nbits = r.d_nbits; da.dphi = h->d_dphi; da.ties = h->d_ties;
@@ -459,7 +447,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
         nvx_fir3_args fa{};
         fa.y2[0] = y2_bufs[0]; fa.y2[1] = y2_bufs[1]; fa.y2_pitch = h->y2_pitch; fa.y2_row = h->d_y2row;
         fa.y3 = h->d_y3[yb]; fa.y3_cap = (size_t)h->y3_cap; fa.y3_base = 0; fa.n_frames = n_frames; fa.n_slots = h->n_slots;
-        fa.part = d_list; fa.n_part = r.n_part; fa.per_part = per_part;
+        fa.part = d_list; fa.n_part = r.n_part; fa.per_part = h->per_in;
         if (r.timed) HIP_TRY(hipEventRecord(r.ev[6], sd));
         HIP_TRY(nvx_launch_fir3(&fa, sd));
         if (r.timed) HIP_TRY(hipEventRecord(r.ev[7], sd));
@@ -492,12 +480,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     if (part) h->partial_launches++;
     // from the first partial launch on the streams are on their own clocks (every launch carries a list) -- until they
     // have come together again: same parity, same position
-    h->diverged = with_list;
-    if (h->diverged) {
-        bool together = true;
-        for (int s = 1; s < h->n_in && together; s++) together = h->parity[s] == h->parity[0] && h->g0s[s] == h->g0s[0];
-        if (together) h->diverged = false;
-    }
+    h->diverged = with_list && !streams_together(h);
     return NVX_OK;
 }
 
@@ -589,7 +572,7 @@ int nvx_collect_locked(nvx_handle *h, uint64_t upto)
             std::atomic<int> bad_slot{ -1 };
             // the chains of this launch: every slot, or (a launch with a participant list) the 2 * per_part slots of each
             // participating input stream -- the other slots' rows of this result hold nothing from this launch
-            const int per_slots = 2 * (h->cfg.wideband ? NVX_WB_SUBBANDS : 1);
+            const int per_slots = 2 * h->per_in;
             const int n_chains = r.n_part ? r.n_part * per_slots : h->n_slots;
             auto work = [&](int lo, int hi) {
                 for (int k = lo; k < hi; k++) {
@@ -780,10 +763,9 @@ extern "C" int nvx_enable_debug(nvx_handle *h, int enabled)
     if (!h) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     HIP_TRY(hipSetDevice(h->cfg.device));
-    if (h->launch_done_valid) HIP_TRY(hipEventSynchronize(h->launch_done));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
     if (enabled && !h->d_dphi) HIP_TRY(hipMalloc(&h->d_dphi, (size_t)h->n_slots * h->y3_cap * sizeof(double)));
-    if (!enabled && h->d_dphi) { hipFree(h->d_dphi); h->d_dphi = nullptr; }
+    if (!enabled && h->d_dphi) { (void)hipFree(h->d_dphi); h->d_dphi = nullptr; }
     return NVX_OK;
 }
 
@@ -793,9 +775,8 @@ extern "C" int nvx_debug_cascade_state(nvx_handle *h, int stream, void *buf, siz
     if (!h || !buf || stream < 0 || stream >= h->n_streams || bytes != (size_t)NVX_CASCADE_STATE_BYTES) { nvx_set_error("nvx_debug_cascade_state: bad argument (a block is %d bytes)", NVX_CASCADE_STATE_BYTES); return NVX_ERR_ARG; }
     std::lock_guard<std::mutex> lk(h->mu);
     HIP_TRY(hipSetDevice(h->cfg.device));
-    if (h->launch_done_valid) HIP_TRY(hipEventSynchronize(h->launch_done));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    const int in = h->cfg.wideband ? stream / NVX_WB_SUBBANDS : stream;      // the input stream whose parity the block follows
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
+    const int in = stream / h->per_in;                                      // the input stream whose parity the block follows
     uint8_t *blk = h->d_cstate[h->parity[in]] + (size_t)stream * NVX_CASCADE_STATE_BYTES;
     if (write) HIP_TRY(hipMemcpy(blk, buf, bytes, hipMemcpyHostToDevice));
     else HIP_TRY(hipMemcpy(buf, blk, bytes, hipMemcpyDeviceToHost));
@@ -825,9 +806,7 @@ extern "C" int nvx_debug_advance_clock(nvx_handle *h, int stream, uint64_t perio
     if (h->ended[stream]) { nvx_set_error("nvx_debug_advance_clock: stream %d has ended", stream); return NVX_ERR_STATE; }
     HIP_TRY(hipSetDevice(h->cfg.device));
     { int rc = nvx_collect_locked(h); if (rc != NVX_OK) return rc; }
-    if (h->launch_done_valid) HIP_TRY(hipEventSynchronize(h->launch_done));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream2));
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
     const unsigned long long g_old = h->g0s[stream];
     // (the priming thresholds are the one thing that is NOT periodic: a stream that has not passed them would skip its priming)
     if (g_old < 3 * NVX_FRAME_Y3) { nvx_set_error("nvx_debug_advance_clock: stream %d is still priming (%llu samples at 900 S/s; the timing filter is primed at 582)", stream, g_old); return NVX_ERR_STATE; }
@@ -841,9 +820,7 @@ extern "C" int nvx_debug_advance_clock(nvx_handle *h, int stream, uint64_t perio
     seal[1] = ((unsigned long long)(unsigned)stream << 32) | third_new;
     HIP_TRY(hipMemcpy(entry, seal, sizeof seal, hipMemcpyHostToDevice));
     h->g0s[stream] = g_new;
-    bool together = true;
-    for (int s = 1; s < h->n_in && together; s++) together = h->parity[s] == h->parity[0] && h->g0s[s] == h->g0s[0];
-    h->diverged = !together;
+    h->diverged = !streams_together(h);
     return NVX_OK;
 }
 
@@ -856,7 +833,7 @@ extern "C" size_t nvx_debug_y3(nvx_handle *h, int stream, int chain, double *out
     size_t n = std::min(cap_pairs, (size_t)h->last_n3);
     // a stream whose input has ended (nvx_finish): only the samples its real input produced (the rest of the frame was
     // computed from the zeros behind its last sample and is not part of anything)
-    const int in = h->cfg.wideband ? stream / NVX_WB_SUBBANDS : stream;
+    const int in = stream / h->per_in;
     if (h->ended[in]) n = std::min(n, (size_t)(h->g0s[in] % NVX_FRAME_Y3));
     if (hipMemcpy(out, h->d_y3[(h->launched + 1) & 1] + (size_t)(2 * stream + chain) * h->y3_cap, n * sizeof(double2), hipMemcpyDeviceToHost) != hipSuccess) return 0;
     return n;

@@ -107,14 +107,18 @@ int64_t nvx_now_ns();
 // what nvx_capture_latency / nvx_shim_latency report from a clock (any out pointer may be null)
 void nvx_clock_report(ArrivalClock &c, uint64_t *frames, double *p50_ms, double *p99_ms, double *max_ms, double *last_ms, int reset);
 
+// A HIP resource the handle made (nvx_create): free_handle releases them in reverse order of creation.
+enum class HipRes : uint8_t { stream, event, device, pinned };
+
 struct nvx_handle {
     nvx_config cfg{};
     int n_streams = 0, n_slots = 0, nch = 1;   // n_streams: 252 kS/s-path streams (8 per input in wideband mode)
     int n_in = 0;                      // input streams the caller addresses (= n_streams unless wideband)
+    int per_in = 1;                    // decoded streams per input stream: NVX_WB_SUBBANDS in wideband mode (stream 8 * w + k)
     size_t bit_history = NVX_BIT_HISTORY;
     bool cascade_raw = false;          // the cascade kernel's RAW switch (never set in wideband mode)
     size_t frame_in = 0;               // complex input samples per frame at the input rate
-    uint32_t *d_whist[2] = { nullptr, nullptr };   // wideband handles: the channeliser's 40-sample halo in front of a launch, by stream parity
+    uint32_t *d_whist[2] = { nullptr, nullptr };   // wideband handles: the channeliser's halo in front of a launch (NVX_WB_HALO), by stream parity
     int y3_cap = 0, bits_cap = 0;
     hipStream_t stream = nullptr;      // FIR cascade (or the caller's stream) and H2D staging
     hipStream_t stream2 = nullptr;     // the demodulator (nvx_fir3 of a wideband handle, front, FSM) + D2H of the bits: beside the next cascade launch
@@ -138,7 +142,8 @@ struct nvx_handle {
     std::vector<int> y2row;                    // host copy of the row table: row of slot i, or -1
     size_t y2_pitch = 0; int y2_rows = 0;
     double *d_dd[2] = { nullptr, nullptr };   // demodulator state blocks: a chain reads [its stream's parity], writes the other
-    double *d_dphi = nullptr; int *d_di = nullptr;
+    double *d_dphi = nullptr;          // nvx_enable_debug's buffer: not on the release list (made and freed there)
+    int *d_di = nullptr;
     uint32_t *d_fsm_tab = nullptr;     // bit-period transition table of the demodulator FSM (nvx_fsm.h)
     unsigned short *d_words = nullptr;
     nvx_tie_stats *d_ties = nullptr;   // arg-max margin statistics, cumulative since create / reset
@@ -178,6 +183,8 @@ struct nvx_handle {
     std::vector<Slot> slots;
     std::vector<struct SinkCtx *> sinks;   // user pointers handed to the per-slot character layers
     HostPool pool;                         // character-layer workers, started on first use
+    std::vector<std::pair<HipRes, void *>> made;   // every stream, event and buffer above, as nvx_create made them (the
+                                                   // members are plain views into this list)
     std::mutex mu;
     // push mode staging: two pinned sets [n_streams][stage_cap] of packed IQ words.  Every stream fills ITS current set
     // (cur[s]) and flips to the other one when a launch takes frames from it; set_launch[s][k] = 1 + the number of the

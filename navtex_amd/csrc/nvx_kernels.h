@@ -178,6 +178,7 @@ typedef struct {
 
 /* fused wideband kernel (nvx_wideband_fused.hip): n_wide streams at 2.016 MS/s -> 8 * n_wide decoded 252 kS/s streams */
 #define NVX_WB_SUBBANDS_K 8
+#define NVX_WB_HALO 40             /* raw words of the channeliser's halo in front of a launch, per wideband stream (hist) */
 typedef struct {
     const uint32_t *raw;       /* [n_wide][pitch] packed IQ at 2.016 MS/s                                    */
     size_t pitch, first_sample;

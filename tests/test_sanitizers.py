@@ -107,3 +107,21 @@ def test_push_path_is_clean_under_tsan(tmp_path):
     out = _run_tsan([exe])
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     assert "tsan push ok" in out.stdout
+
+
+def test_handle_lifecycle_is_clean_under_asan(tmp_path):
+    """AddressSanitizer + LeakSanitizer over the life of a handle (nvx_api.cpp) with HIP replaced by host memory that
+    counts every stream, event and buffer and can fail any one creating call: create / destroy (debug buffer included)
+    release everything exactly once, a create that fails at any call unwinds to nothing, nvx_stream_reset(s) restores
+    exactly stream s's carried state to a fresh handle's and nvx_reset all of it -- for every kind of handle
+    (tests/harness/handle_lifecycle.cpp)."""
+    exe = tmp_path / "handle_lifecycle"
+    csrc = ROOT / "navtex_amd" / "csrc"
+    subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                    "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT / 'include'}", f"-I{csrc}",
+                    str(ROOT / "tests" / "harness" / "handle_lifecycle.cpp"), str(csrc / "nvx_api.cpp"), str(csrc / "nvx_fsm_host.cpp"),
+                    "-x", "c", str(csrc / "nvx_sitor.c"), "-o", str(exe), "-lpthread"], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=600,
+                         env={"ASAN_OPTIONS": "detect_leaks=1", "PATH": "/usr/bin:/bin"})
+    assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
+    assert "handle lifecycle ok" in out.stdout
