@@ -129,13 +129,19 @@ struct Stage0Cic3 {
         c_prev = 0; t_prev = 0;
     }
     __device__ __forceinline__ static int rot1(int v) { return __builtin_amdgcn_mov_dpp(v, 0x13C, 0xF, 0xF, false); }   // wave_ror:1: lane l reads lane l-1, lane 0 lane 63
-    // a dot product that STARTS a sum: the VOP3P form, whose third operand is the inline constant 0.  (The builtin with a
-    // zero accumulator compiles to v_mov_b32 acc, 0 + v_dot2c_i32_i16: six moves per load -- r6, counted in the ISA.)
-    __device__ __forceinline__ static int dot2_first(nvx_short2 a, unsigned w)
+    // the dot products that START two sums (b and c, same samples): the VOP3P form, whose third operand is the inline
+    // constant 0.  (The builtin with a zero accumulator compiles to v_mov_b32 acc, 0 + v_dot2c_i32_i16: six moves per load
+    // -- r6, counted in the ISA.)  Wait states: hipcc pads no hazard whose producer is inside an asm string, and LLVM's
+    // gfx950 hazard model wants 3 between a DOT's result and any reader but the same opcode taking it as accumulator
+    // (GCNHazardRecognizer, DotWriteDifferentVALURead) -- here the first reader is the v_dot2c_i32_i16 that adds the
+    // second product, a different opcode.  The s_nop 2 that ends the string gives c its 3 and b 4, whatever the compiler
+    // schedules behind the statement; both in one statement, so one pad per load.  tests/test_isa.py checks every asm result.
+    __device__ __forceinline__ static void dot2_first(nvx_short2 a, unsigned wb, unsigned wc, int &b, int &c)
     {
-        int r;
-        asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(w));
-        return r;
+        asm("v_dot2_i32_i16 %0, %2, %3, 0\n\t"
+            "v_dot2_i32_i16 %1, %2, %4, 0\n\t"
+            "s_nop 2"
+            : "=&v"(b), "=v"(c) : "v"(a), "v"(wb), "v"(wc));    // b is written before wc is read: early clobber
     }
     // r6: 29 vector instructions per load where the compiler had made 34 of the round-2 form (own sums and partner's sums
     // side by side, three adds to join them: PMC 62.9 vector instructions per load in the kernel where the design counted
@@ -147,8 +153,9 @@ struct Stage0Cic3 {
         const nvx_short2 m01 = as_short2(__builtin_amdgcn_perm(v.y, v.x, sel_mine)), m23 = as_short2(__builtin_amdgcn_perm(v.w, v.z, sel_mine));
         const nvx_short2 o01 = as_short2(__builtin_amdgcn_perm(v.y, v.x, sel_other)), o23 = as_short2(__builtin_amdgcn_perm(v.w, v.z, sel_other));
         int oa = __builtin_amdgcn_sdot2(o01, as_short2(wa0), 256, false); oa = __builtin_amdgcn_sdot2(o23, as_short2(wa1), oa, false);   // + 256: round half up
-        int ob = dot2_first(o01, wb0); ob = __builtin_amdgcn_sdot2(o23, as_short2(wb1), ob, false);
-        int oc = dot2_first(o01, wc0); oc = __builtin_amdgcn_sdot2(o23, as_short2(wc1), oc, false);
+        int ob, oc;
+        dot2_first(o01, wb0, wc0, ob, oc);
+        ob = __builtin_amdgcn_sdot2(o23, as_short2(wb1), ob, false); oc = __builtin_amdgcn_sdot2(o23, as_short2(wc1), oc, false);
         int A = dpp_swap_pairs(oa); A = __builtin_amdgcn_sdot2(m01, as_short2(wa0), A, false); A = __builtin_amdgcn_sdot2(m23, as_short2(wa1), A, false);
         int B = dpp_swap_pairs(ob); B = __builtin_amdgcn_sdot2(m01, as_short2(wb0), B, false); B = __builtin_amdgcn_sdot2(m23, as_short2(wb1), B, false);
         int C = dpp_swap_pairs(oc); C = __builtin_amdgcn_sdot2(m01, as_short2(wc0), C, false); C = __builtin_amdgcn_sdot2(m23, as_short2(wc1), C, false);

@@ -238,3 +238,149 @@ print(h.hexdigest())
         assert out.returncode == 0, out.stderr[-2000:]
         digests.append(out.stdout.strip().splitlines()[-1])
     assert digests[0] == digests[1] == digests[2] and len(digests[0]) == 64
+
+
+# The input of the rails test below, and the checks it runs in each unit form (a subprocess each: the form is read once
+# per process).  CIC^3 geometry: a 1-KiB load is 256 raw samples (lane l holds 4l .. 4l+3: the pair 62 / 63 holds the
+# last block, whose C and t cross to the next load by the wave rotation and to the next unit through the state block), a
+# pass 2048, a frame 645 120 (a unit), a third 215 040 (a unit in a launch's last frame or in independent launches), the
+# pre-roll 9 passes = 18 432 in front of a unit that rebuilds its histories.
+_RAILS3 = '''
+import sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import numpy as np, navtex_amd as nv, oracle_binding as ob
+FR, FY = nv.FRAME_RAW, nv.FRAME_Y3
+LOAD, PRE, THIRD = 256, 9 * 2048, FR // 3
+F, F2 = 4, 2
+HI, LO = 32767, -32768
+ALT = np.where(np.arange(1 << 16) & 1, HI, LO).astype(np.int16)
+rng = np.random.default_rng(303)
+
+
+def rail(kind, m):
+    """m samples of rail kind 0..4: both +full scale, both -full scale, I up / Q down, I down / Q up, alternating (I, Q opposite)."""
+    if kind == 4:
+        return np.stack([ALT[:m], -1 - ALT[:m]], 1)
+    return np.tile(np.array([(HI, HI), (LO, LO), (HI, LO), (LO, HI)][kind], np.int16), (m, 1))
+
+
+def make_input(n, s):
+    raw = rng.integers(LO, HI + 1, size=(n, 2), dtype=np.int16)            # full-range uniform noise
+    at = 1000 + 977 * s
+    for k in range(5):                                                      # long stretches of every kind of rail
+        raw[at + 70000 * k:at + 70000 * k + 50000] = rail(k, 50000)
+    # samples 240 .. 271 of 600 consecutive loads: the last block pair of a load (lanes 60 .. 63) and the first of the next,
+    # a different kind of rail from load to load, noise in between
+    base = (at + 360000) // LOAD * LOAD
+    for j in range(600):
+        raw[base + LOAD * j + 240:base + LOAD * j + 272] = rail(j % 5, 32)
+    # a step from one rail to another exactly at every unit boundary (frames, thirds; the launch boundary is one of them)
+    # and at the first sample of the pre-roll window in front of each
+    for k in range(1, n // THIRD):
+        for i, b in enumerate((k * THIRD, k * THIRD - PRE)):
+            raw[b - 600:b] = rail((k + i) % 5, 600); raw[b:b + 600] = rail((k + i + 2) % 5, 600)
+    # the carriers of both chains (+-14 kHz) as full-scale square waves: nothing but rails in the input, and 900 S/s output
+    # near the largest the cascade can produce, across a frame boundary and a third-of-frame boundary
+    t = np.arange(80000)
+    for b, f in ((2 * FR, 14000), (3 * FR + THIRD, -14000)):
+        ph = 2 * np.pi * f * (t + b) / nv.RATE_RAW
+        raw[b - 40000:b + 40000] = np.stack([np.where(np.cos(ph) >= 0, HI, LO), np.where(np.sin(ph) >= 0, HI, LO)], 1)
+    return raw
+
+
+def stage0_reaches_the_rails(raw):
+    y0 = ob.stage0_cic3(raw)
+    assert y0.max() == HI and y0.min() == LO, (y0.min(), y0.max())
+
+
+def oracle_pipe(mask, raw, n3):
+    r = ob.Pipe(chain_mask=mask, charlayer=False, tap_y3=n3)
+    r.set_stage0(3)
+    r.push_raw(raw)
+    for c in range(2):          # the full-scale carrier of each enabled chain reaches the 900 S/s output: |y3| ~ 35 600
+        assert not (mask >> c) & 1 or np.abs(r.y3(c)).max() > 30000.0, (mask, c)
+    return r
+
+
+def same(got, want, what):
+    assert got.shape == want.shape and np.array_equal(got.view(np.uint64), want.view(np.uint64)), (what, got.shape, want.shape)
+    assert np.abs(want).max() > 300.0, what                                 # not near-silence: the noise alone gives ~700 per frame
+
+
+checked_resident = 0
+n = (F + F2) * FR
+for masks in ([1, 1, 2], [3, 2, 3]):                                        # the one-chain and the two-chain kernel
+    S = len(masks)
+    raw = np.stack([make_input(n, s) for s in range(S)])
+    stage0_reaches_the_rails(raw[0])
+    refs = [oracle_pipe(masks[s], raw[s], (F + F2) * FY) for s in range(S)]
+    buf = nv.DeviceBuffer(S * n * 4)
+    buf.upload(raw)
+    with nv.Pipeline(n_streams=S, raw_rate=True, chain_masks=masks, max_frames=F, char_layer=False, stage0_order=3) as p:
+        for f0, k in ((0, F), (F, F2)):
+            p.process_resident(buf, n, f0, k); p.fetch()
+            for s in range(S):
+                for c in range(2):
+                    if (masks[s] >> c) & 1:
+                        same(p.debug_y3(s, c), np.ascontiguousarray(refs[s].y3(c)[f0 * FY:(f0 + k) * FY]), (masks, s, c, f0))
+                        checked_resident += 1
+        for s in range(S):
+            for c in range(2):
+                assert p.bits(s, c) == (refs[s].bits(c) if (masks[s] >> c) & 1 else ""), (masks, s, c)
+    buf.free()
+
+# push mode, ragged pushes, streams launched as soon as each has a frame (eager_launch): the streams come apart in time, so
+# the launches name their streams -- the list kernels -- and every launch is held against the oracle right after its push
+checked_push = 0
+n = 4 * FR
+for masks in ([1, 2], [3, 1]):
+    S = len(masks)
+    raw = np.stack([make_input(n, s) for s in range(S)])
+    refs = [oracle_pipe(masks[s], raw[s], 4 * FY) for s in range(S)]
+    with nv.Pipeline(n_streams=S, raw_rate=True, chain_masks=masks, max_frames=2, push_mode=True, eager_launch=True,
+                     char_layer=False, stage0_order=3) as p:
+        pos = [0] * S
+        seen = [[0, 0] for _ in range(S)]                                   # frames checked per (stream, chain)
+        while min(pos) < n:
+            s = int(rng.integers(0, S)) if max(pos) < n else pos.index(min(pos))
+            if pos[s] >= n:
+                continue
+            m = int(min(n - pos[s], rng.choice([1, 7, 255, 257, 2047, 2049, 18433, int(rng.integers(1, FR))])))   # < a frame: one launch at most
+            before = [p.stream_stats(t)[1] for t in range(S)]
+            p.push(s, raw[s, pos[s]:pos[s] + m]); pos[s] += m
+            for t in range(S):
+                after = p.stream_stats(t)[1]
+                if after == before[t]:
+                    continue
+                for c in range(2):
+                    if (masks[t] >> c) & 1:
+                        same(p.debug_y3(t, c), np.ascontiguousarray(refs[t].y3(c)[before[t] * FY:after * FY]), (masks, t, c, before[t]))
+                        seen[t][c] += after - before[t]
+        p.flush()
+        assert [p.stream_stats(t)[1] for t in range(S)] == [4] * S
+        assert p.stream_stats(0)[2] > 0, "no launch named its streams: the list kernels were not run"
+        for t in range(S):
+            for c in range(2):
+                assert seen[t][c] == (4 if (masks[t] >> c) & 1 else 0), (masks, t, c, seen[t][c])
+                checked_push += seen[t][c]
+                assert p.bits(t, c) == (refs[t].bits(c) if (masks[t] >> c) & 1 else ""), (masks, t, c)
+print("rails ok", checked_resident, checked_push)
+'''
+
+
+@pytest.mark.gpu
+def test_full_scale_rails_through_every_third_order_kernel_and_unit_form(tmp_path):
+    """The third-order stage 0 at the int16 rails, every one of its four kernels, in every unit form, against the oracle:
+    full-range noise with long stretches of each kind of rail; rails over samples 240 .. 271 of 600 consecutive loads
+    (the lane pair 62 / 63 whose C and t the wave rotation and the state block carry on); a step from one rail to another
+    exactly at every frame, third-of-frame and launch boundary and at the first sample of every pre-roll window.  Resident
+    input through the one- and two-chain kernels (two launches), and host input in ragged pushes through the list kernels:
+    every launch's 900 S/s output as fp64 bit patterns and the bits == oracle stage 0 -> oracle cascade.  Waiting and
+    pre-rolling hand-over, independent units, and the launcher's own choice, a subprocess each."""
+    script = tmp_path / "rails3.py"
+    script.write_text(_RAILS3)
+    for env in (dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="0"), dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="1"), dict(NVX_INDEPENDENT="1"), {}):
+        out = subprocess.run([sys.executable, str(script), str(ROOT)], capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
+        assert out.returncode == 0, (env, out.stderr[-3000:])
+        # resident: (3 + 5 enabled chains) x 2 launches; push: (2 + 3 enabled chains) x 4 frames
+        assert out.stdout.strip().splitlines()[-1] == "rails ok 16 20", (env, out.stdout[-500:])
