@@ -406,7 +406,7 @@ NVX_API int   nvx_fsm_selftest(uint32_t seed, int periods);
  * through three frames (the priming thresholds of the timing filter are the one thing that is not periodic): NVX_ERR_STATE. */
 #define NVX_CLOCK_PERIOD 163296
 NVX_API int   nvx_debug_advance_clock(nvx_handle *h, int stream, uint64_t periods);
-/* allocate (1) / release (0) the delta-phi debug buffer used by nvx_debug_dphi */
+/* allocate (1) / release (0) the demodulator's debug buffers: delta-phi for nvx_debug_dphi, and the bit-timing taps */
 NVX_API int   nvx_enable_debug(nvx_handle *h, int enabled);
 /* test / diagnostics hook: the carried FIR state block of one decoded stream -- the block the stream's NEXT launch will
  * read: filter histories as fp64 pairs, then the seal (nvx_cascade_integrity_stats) -- copied to host memory (write = 0)

@@ -336,6 +336,15 @@ class Pipeline(HandleStats):
         n = lib.nvx_debug_dphi(self._h, stream, chain, N.as_ptr(out), out.size)
         return out[:n]
 
+    def debug_timing(self, stream: int = 0, chain: int = 0) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """The bit-timing filter of the last launch (nvx_debug_timing): (|corr|, class sums) per 900 S/s sample and the
+        words per bit period (uint16: nine window decisions, arg-max << 12).  Needs enable_debug()."""
+        cap = self.max_frames * FRAME_Y3
+        corr, csum = np.empty(cap, dtype=np.float64), np.empty(cap, dtype=np.float64)
+        words = np.empty((cap + 8) // 9, dtype=np.uint16)
+        n = lib.nvx_debug_timing(self._h, stream, chain, N.as_ptr(corr), N.as_ptr(csum), N.as_ptr(words), cap)
+        return corr[:n], csum[:n], words[:(n + 8) // 9]
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             lib.nvx_destroy(self._h)

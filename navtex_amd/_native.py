@@ -94,6 +94,7 @@ def _load() -> C.CDLL:
         "nvx_stream_stats": (i, [vp, i, C.POINTER(i), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "nvx_kernel_time_stats": (i, [vp, i, C.POINTER(C.c_double), C.POINTER(C.c_uint64), i]),
         "nvx_debug_y3": (sz, [vp, i, i, vp, sz]), "nvx_debug_dphi": (sz, [vp, i, i, vp, sz]),
+        "nvx_debug_timing": (sz, [vp, i, i, vp, vp, vp, sz]),
         "nvx_device_count": (i, []), "nvx_device_alloc": (vp, [i, sz]), "nvx_device_free": (None, [i, vp]),
         "nvx_memcpy_h2d": (i, [i, vp, vp, sz]), "nvx_memcpy_d2h": (i, [i, vp, vp, sz]), "nvx_device_sync": (i, [i]),
         "nvx_stream_create": (vp, [i]), "nvx_stream_destroy": (None, [i, vp]),

@@ -96,6 +96,12 @@ static inline bool streams_together(const nvx_handle *h)
     return true;
 }
 
+// nvx_enable_debug's buffers (debug taps of the demodulator), made together and released together
+static void free_debug(nvx_handle *h)
+{
+    for (double **p : { &h->d_dphi, &h->d_corr, &h->d_csum }) { (void)hipFree(*p); *p = nullptr; }
+}
+
 static void free_handle(nvx_handle *h)
 {
     if (!h) return;
@@ -103,7 +109,7 @@ static void free_handle(nvx_handle *h)
     (void)hipSetDevice(h->cfg.device);
     (void)drain(h);
     snprintf(g_err, sizeof g_err, "%s", err.c_str());
-    (void)hipFree(h->d_dphi);
+    free_debug(h);
     for (auto it = h->made.rbegin(); it != h->made.rend(); ++it) {      // the streams, made first, go last
         switch (it->first) {
         case HipRes::stream: (void)hipStreamDestroy((hipStream_t)it->second); break;
@@ -408,6 +414,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     da.dstate[0] = h->d_dd[p0]; da.dstate[1] = h->d_dd[p0 ^ 1];     // (read, write) without a list; [0], [1] with one
     da.state_i = h->d_di; da.fsm_table = h->d_fsm_tab; da.words = h->d_words;
     da.bits = r.d_bits; da.bits_cap = h->bits_cap; da.nbits = r.d_nbits; da.dphi = h->d_dphi; da.ties = h->d_ties;
+    da.corr = h->d_corr; da.csum = h->d_csum;
 
     // cascade on `st`: it may not overwrite y3[yb] before the demodulator of two launches ago has read it
     if (h->demod_pending[yb]) HIP_TRY(hipStreamWaitEvent(st, h->demod_done[yb], 0));
@@ -764,8 +771,14 @@ extern "C" int nvx_enable_debug(nvx_handle *h, int enabled)
     std::lock_guard<std::mutex> lk(h->mu);
     HIP_TRY(hipSetDevice(h->cfg.device));
     { int rc = drain(h); if (rc != NVX_OK) return rc; }
-    if (enabled && !h->d_dphi) HIP_TRY(hipMalloc(&h->d_dphi, (size_t)h->n_slots * h->y3_cap * sizeof(double)));
-    if (!enabled && h->d_dphi) { (void)hipFree(h->d_dphi); h->d_dphi = nullptr; }
+    if (enabled && !h->d_dphi) {
+        const size_t bytes = (size_t)h->n_slots * h->y3_cap * sizeof(double);
+        for (double **p : { &h->d_dphi, &h->d_corr, &h->d_csum }) {
+            const hipError_t e = hipMalloc(p, bytes);
+            if (e != hipSuccess) { *p = nullptr; free_debug(h); nvx_set_error("nvx_enable_debug: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); return NVX_ERR_NOMEM; }
+        }
+    }
+    if (!enabled) free_debug(h);
     return NVX_OK;
 }
 
@@ -847,6 +860,23 @@ extern "C" size_t nvx_debug_dphi(nvx_handle *h, int stream, int chain, double *o
     hipDeviceSynchronize();
     size_t n = std::min(cap, (size_t)h->last_n3);
     if (hipMemcpy(out, h->d_dphi + (size_t)(2 * stream + chain) * h->y3_cap, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    return n;
+}
+
+extern "C" size_t nvx_debug_timing(nvx_handle *h, int stream, int chain, double *corr, double *csum, uint16_t *words, size_t cap)
+{
+    if (!h || stream < 0 || stream >= h->n_streams || chain < 0 || chain > 1) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if ((corr || csum) && !h->d_corr) return 0;
+    hipSetDevice(h->cfg.device);
+    hipDeviceSynchronize();
+    size_t n = std::min(cap, (size_t)h->last_n3);
+    const int in = stream / h->per_in;                                      // an ended stream: its real samples (nvx_debug_y3)
+    if (h->ended[in]) n = std::min(n, (size_t)(h->g0s[in] % NVX_FRAME_Y3));
+    const size_t slot = (size_t)(2 * stream + chain);
+    if (corr && hipMemcpy(corr, h->d_corr + slot * h->y3_cap, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    if (csum && hipMemcpy(csum, h->d_csum + slot * h->y3_cap, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return 0;
+    if (words && hipMemcpy(words, h->d_words + slot * (h->y3_cap / 9), (n + 8) / 9 * sizeof(uint16_t), hipMemcpyDeviceToHost) != hipSuccess) return 0;
     return n;
 }
 

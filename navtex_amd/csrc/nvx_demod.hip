@@ -217,6 +217,8 @@ __device__ __forceinline__ void front_sequential(const nvx_demod_args &a, int ch
     const double *st = ch.st_rd;
     const double2 *y3 = a.y3 + (size_t)slot * a.y3_cap + a.y3_base;
     double *dphi_out = a.dphi ? a.dphi + (size_t)slot * a.y3_cap + a.y3_base : nullptr;
+    double *corr_out = a.corr ? a.corr + (size_t)slot * a.y3_cap + a.y3_base : nullptr;
+    double *csum_out = a.csum ? a.csum + (size_t)slot * a.y3_cap + a.y3_base : nullptr;
     const double *hist = st + DS_Y3;                     // read in place: only the first 4 samples need it
     if (tid < 8) { s_dphi[tid] = st[DS_DPHI + tid]; s_S[tid] = st[DS_S + tid]; }
     for (int i = tid; i < 567; i += NVX_FRONT_THREADS) s_C[i] = st[DS_C + i];
@@ -246,6 +248,8 @@ __device__ __forceinline__ void front_sequential(const nvx_demod_args &a, int ch
         for (int L = tid; L < tl; L += NVX_FRONT_THREADS)
             s_S[8 + L] = (gt + L >= G_CB) ? front_class_sum(&s_C[567 + L], t_cb + (unsigned)L) : 0.0;
         __syncthreads();
+        if (corr_out)                                    // debug taps (set together): one uniform branch per tile, off the compute loops
+            for (int L = tid; L < tl; L += NVX_FRONT_THREADS) { corr_out[ta + L] = s_C[567 + L]; csum_out[ta + L] = s_S[8 + L]; }
         for (int M = tid; M < tl9; M += NVX_FRONT_THREADS) {
             const int L = 9 * M + (G_CSA % 9);             // (L >= tl: the stream ended before this period's timing evaluation)
             a.words[(size_t)slot * (a.y3_cap / 9) + (ta / 9 + M)] = front_word(&s_D[9 * M], &s_S[L], L < tl && gt + L >= G_CSA, ties);
@@ -311,6 +315,8 @@ __global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front_tiles(nvx_d
     const int tl = min(DTL, a.n3 - ta);
     const double2 *y3 = a.y3 + (size_t)slot * a.y3_cap + a.y3_base;
     double *dphi_out = a.dphi ? a.dphi + (size_t)slot * a.y3_cap + a.y3_base : nullptr;
+    double *corr_out = a.corr ? a.corr + (size_t)slot * a.y3_cap + a.y3_base : nullptr;
+    double *csum_out = a.csum ? a.csum + (size_t)slot * a.y3_cap + a.y3_base : nullptr;
     const unsigned long long g_ta = ch.g0 + (unsigned long long)ta;
 
     for (int i = tid; i < FRONT_LOOKBACK + tl; i += NVX_FRONT_THREADS) {
@@ -332,6 +338,9 @@ __global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front_tiles(nvx_d
     for (int i = tid; i < 2 + tl; i += NVX_FRONT_THREADS)
         p_S[i] = (g_ta - 2 + (unsigned long long)i >= G_CB) ? front_class_sum(&p_C[566 + i], t_cb + (unsigned)i) : 0.0;
     __syncthreads();
+    // debug taps (set together): the tile's own samples only -- its look-back belongs to the tile in front
+    if (corr_out)
+        for (int i = tid; i < tl; i += NVX_FRONT_THREADS) { corr_out[ta + i] = p_C[FRONT_LOOKBACK - 8 + i]; csum_out[ta + i] = p_S[2 + i]; }
     // period M of the tile: decisions p_D[9M .. 9M+8]; evaluation on its sample 6 with S of samples 9M-2 .. 9M+6 = p_S[9M ..]
     for (int M = tid; M < tl / 9; M += NVX_FRONT_THREADS)
         a.words[(size_t)slot * (a.y3_cap / 9) + (ta / 9 + M)] = front_word(&p_D[9 * M], &p_S[9 * M], g_ta + 9 * M + (G_CSA % 9) >= G_CSA, ties);

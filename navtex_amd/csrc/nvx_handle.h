@@ -142,7 +142,8 @@ struct nvx_handle {
     std::vector<int> y2row;                    // host copy of the row table: row of slot i, or -1
     size_t y2_pitch = 0; int y2_rows = 0;
     double *d_dd[2] = { nullptr, nullptr };   // demodulator state blocks: a chain reads [its stream's parity], writes the other
-    double *d_dphi = nullptr;          // nvx_enable_debug's buffer: not on the release list (made and freed there)
+    double *d_dphi = nullptr;          // nvx_enable_debug's buffers: not on the release list (made and freed there)
+    double *d_corr = nullptr, *d_csum = nullptr;
     int *d_di = nullptr;
     uint32_t *d_fsm_tab = nullptr;     // bit-period transition table of the demodulator FSM (nvx_fsm.h)
     unsigned short *d_words = nullptr;

@@ -155,6 +155,8 @@ typedef struct {
     unsigned short *words;     /* [n_slots][y3_cap/9] per-bit-period hand-over, front -> fsm (rows 16-byte aligned) */
     uint8_t *bits; int bits_cap; int *nbits;   /* bits: packed, B = 1, LSB first; bits_cap bytes (multiple of 4) per slot */
     double *dphi;              /* optional debug tap, same layout as y3 (or NULL)      */
+    double *corr, *csum;       /* optional debug taps of the bit-timing filter: |corr| and the class sum of every sample, */
+                               /* same layout as y3 (or NULL; set together with dphi)                                     */
     nvx_tie_stats *ties;       /* cumulative arg-max margin statistics (never NULL)    */
 } nvx_demod_args;
 

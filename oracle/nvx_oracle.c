@@ -269,6 +269,7 @@ static void bd_in_bit_sync(nvxo_dec *d, int offset)        /* decoder.C:62-70 */
 
 static void bs_sample(nvxo_dec *d, double ds)              /* decoder.C:142-255 */
 {
+    d->last_corr = NAN; d->last_csum = NAN; d->last_argmax = -1;
     d->dab[d->dab_index] = ds;
     d->dab_index++;
     if (d->dab_index == NVXO_SPB) { d->dab_index = 0; d->dab_primed = 1; }
@@ -281,6 +282,7 @@ static void bs_sample(nvxo_dec *d, double ds)              /* decoder.C:142-255 
             j++; j %= NVXO_SPB;
         }
         d->cb[d->cb_index] = fabs(temp);
+        d->last_corr = d->cb[d->cb_index];
         d->cb_index++;
         if (d->cb_index == NVXO_CORR_N) { d->cb_index = 0; d->cb_primed = 1; }
     }
@@ -289,6 +291,7 @@ static void bs_sample(nvxo_dec *d, double ds)              /* decoder.C:142-255 
         double temp = 0.0;
         for (int i = d->csa_index; i < NVXO_CORR_N; i += NVXO_SPB) temp += d->cb[i];
         d->csa[d->csa_index] = temp;
+        d->last_csum = temp;
         d->csa_index++;
         if (d->csa_index == NVXO_SPB) { d->csa_index = 0; d->csa_primed = 1; }
     }
@@ -299,6 +302,7 @@ static void bs_sample(nvxo_dec *d, double ds)              /* decoder.C:142-255 
             int max_index = 0;   /* reference leaves it uninitialised; sums are >= 0 > -1 so it is always set */
             for (int i = 0; i < NVXO_SPB; i++)
                 if (d->csa[i] > temp_max) { temp_max = d->csa[i]; max_index = i; }
+            d->last_argmax = max_index;
             if (!(d->prev_offset == -1 || max_index == d->prev_offset)) {
                 if (max_index > d->prev_offset) {
                     if (max_index - d->prev_offset > 4) max_index = (d->prev_offset - 1 + NVXO_SPB) % NVXO_SPB;
@@ -389,6 +393,30 @@ size_t nvxo_decode_with(const double *y3, size_t n3, char *bits_out, nvxo_atan2_
         if (b) bits_out[nb++] = (char)b;
     }
     if (dphi_mismatch) *dphi_mismatch = mism;
+    return nb;
+}
+
+size_t nvxo_decode_taps(const double *y3, size_t n3, char *bits_out, nvxo_atan2_fn fn, double *dphi, double *corr, double *csum,
+                        int *argmax, char *bit_at)
+{
+    nvxo_dec d; nvxo_dec_init(&d);
+    size_t nb = 0;
+    for (size_t k = 0; k < n3; k++) {
+        const double sampleI = y3[2 * k], sampleQ = y3[2 * k + 1];
+        const double prodReal = sampleI * d.prevI + sampleQ * d.prevQ;       /* decoder.C:48-49 */
+        const double prodImg  = sampleQ * d.prevI - sampleI * d.prevQ;
+        const double result = fn ? fn(prodImg, prodReal) : atan2(prodImg, prodReal);
+        d.prevI = sampleI; d.prevQ = sampleQ;
+        bs_sample(&d, result);
+        if (dphi) dphi[k] = result;
+        if (corr) corr[k] = d.last_corr;
+        if (csum) csum[k] = d.last_csum;
+        if (argmax) argmax[k] = d.last_argmax;
+        int b = bd_sample(&d, sampleI, sampleQ);
+        if (bit_at) bit_at[k] = (char)b;
+        if (b && bits_out) bits_out[nb] = (char)b;
+        if (b) nb++;
+    }
     return nb;
 }
 

@@ -76,6 +76,8 @@ typedef struct nvxo_dec {
     /* taps for tests (not reference state) */
     double last_dphi;
     int    last_sync;              /* offset passed to bd_in_bit_sync this sample, or -1 */
+    double last_corr, last_csum;   /* |corr| and class sum written this sample, NaN while unprimed */
+    int    last_argmax;            /* arg-max of this sample's timing evaluation before the slew limiter, or -1 */
 } nvxo_dec;
 void nvxo_dec_init(nvxo_dec *d);
 /* returns 0 (no bit), 'B' or 'Y' */
@@ -91,6 +93,13 @@ size_t nvxo_decode_inject(const double *y3, size_t n3, char *bits_out, size_t at
  * differs in the last bit ever changes a decoded bit.                                    */
 typedef double (*nvxo_atan2_fn)(double, double);
 size_t nvxo_decode_with(const double *y3, size_t n3, char *bits_out, nvxo_atan2_fn fn, size_t *dphi_mismatch);
+/* test hook: nvxo_decode_with (no mismatch count) recording the bit-timing filter per sample k, as bs_sample computes
+ * it (decoder.C:142-215): dphi[k]; corr[k] = |corr| written at k (k >= 8, else NaN); csum[k] = class sum written at k
+ * (k >= 574, else NaN); argmax[k] = first maximum over the nine class sums at a timing evaluation (k >= 582, every
+ * ninth sample), before the slew limiter, else -1; bit_at[k] = the bit ('B' / 'Y') decided at k -- the last sample of
+ * the window the FSM picked -- else 0.  Every output array is optional (NULL); returns the number of bits.          */
+size_t nvxo_decode_taps(const double *y3, size_t n3, char *bits_out, nvxo_atan2_fn fn, double *dphi, double *corr, double *csum,
+                        int *argmax, char *bit_at);
 
 /* ---- SITOR-B character layer (nav_b_sm.h / nav_b_sm.C) -------------------- */
 typedef void (*nvxo_msg_cb)(void *user, const char *bbbb, const char *message, int freq);

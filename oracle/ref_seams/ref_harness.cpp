@@ -31,6 +31,12 @@
 //       sample n -- what 27.6 days of running bring about by themselves (decoder.C:75: it is
 //       incremented for ever).  The member is reached by giving THIS translation unit a public view
 //       of the class; decoder.o is the unmodified reference object and the layout is the same.
+//   ref_taps             in out       (SEAM_DEC built with SEAM_TAPS: a binary of its own, so that a ref_dec built
+//                                      before it existed is never asked for it)
+//       the decoder seam, and after every sample_in the decoder's bit-timing filter (decoder.C:142-197) read through
+//       the same view: .dphi.bin = the newest delta_angle_buffer entry, .corr.bin = the correlation_buffer entry
+//       written by this sample, .csum.bin = the correlation_sumarray entry written by this sample (fp64, one per
+//       sample; NaN before the buffer it comes from is primed).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -187,9 +193,27 @@ int main(int argc, char **argv)
     static decoder dec(&sm);
     const double *y3 = (const double *)in.data();
     size_t n3 = in.size() / 16;
+#if defined(SEAM_TAPS)
+    const bool taps = true;
+#else
+    const bool taps = false;
+#endif
+    std::vector<double> t_dphi, t_corr, t_csum;
     for (size_t n = 0; n < n3; n++) {
         if (probe == "inject" && n == probe_at) dec.bd_seq_nbr = (int)probe_arg;
         dec.sample_in(y3[2 * n], y3[2 * n + 1]);
+        if (!taps) continue;
+        // what this sample wrote: the entry behind each ring's index.  A ring is written from the sample on that primes
+        // the ring in front of it (decoder.C:152 / :157 and :175 / :181 -- the flag is set earlier in the same call)
+        const double nan = __builtin_nan("");
+        t_dphi.push_back(dec.delta_angle_buffer[(dec.dab_index + SAMPLES_PER_BIT - 1) % SAMPLES_PER_BIT]);
+        t_corr.push_back(dec.dab_primed ? dec.correlation_buffer[(dec.cb_index + CORRELATION_BUF_SAMPLE_SIZE - 1) % CORRELATION_BUF_SAMPLE_SIZE] : nan);
+        t_csum.push_back(dec.cb_primed ? dec.correlation_sumarray[(dec.csa_index + SAMPLES_PER_BIT - 1) % SAMPLES_PER_BIT] : nan);
+    }
+    if (taps) {
+        write_all("dphi", t_dphi.data(), t_dphi.size() * 8);
+        write_all("corr", t_corr.data(), t_corr.size() * 8);
+        write_all("csum", t_csum.data(), t_csum.size() * 8);
     }
 #endif
 

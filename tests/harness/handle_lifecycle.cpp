@@ -5,8 +5,8 @@
 // request.  The kernels are never launched on these paths.
 // Checked, for a 252 kS/s handle, raw-rate handles in both stage-0 forms, a push-mode handle and wideband handles with one
 // and two inputs and mixed chain masks:
-//  (a) create then destroy releases every stream, event and buffer exactly once, the streams last; so with the debug
-//      buffer on, and after it has been switched off again;
+//  (a) create then destroy releases every stream, event and buffer exactly once, the streams last; so with the three
+//      debug buffers on, and after they have been switched off again (each made and released once);
 //  (b) whichever creating call of nvx_create fails (hipErrorOutOfMemory), the result is NVX_ERR_NOMEM, no handle and
 //      nothing left outstanding;
 //  (c) with every device buffer filled with a pattern and the per-stream host fields set, nvx_stream_reset(s) leaves the
@@ -124,7 +124,7 @@ static std::vector<Buf> device_buffers(nvx_handle *h)
         { "whist0", h->d_whist[0] }, { "whist1", h->d_whist[1] }, { "y2_0", h->d_y2[0] }, { "y2_1", h->d_y2[1] },
         { "y2row", h->d_y2row }, { "masks", h->d_masks }, { "active", h->d_active }, { "cstate0", h->d_cstate[0] },
         { "cstate1", h->d_cstate[1] }, { "y3_0", h->d_y3[0] }, { "y3_1", h->d_y3[1] }, { "dd0", h->d_dd[0] }, { "dd1", h->d_dd[1] },
-        { "dphi", h->d_dphi }, { "di", h->d_di }, { "fsm_tab", h->d_fsm_tab }, { "words", h->d_words }, { "ties", h->d_ties },
+        { "dphi", h->d_dphi }, { "corr", h->d_corr }, { "csum", h->d_csum }, { "di", h->d_di }, { "fsm_tab", h->d_fsm_tab }, { "words", h->d_words }, { "ties", h->d_ties },
         { "ctrl", h->d_ctrl }, { "in", h->d_in } };
     for (int k = 0; k < RESULT_SLOTS; k++) {
         v.push_back({ "bits" + std::to_string(k), h->res[k].d_bits });
@@ -221,12 +221,31 @@ static void lifecycle(const char *what, nvx_config c)
         nvx_handle *h = create(c);
         // every device buffer the handle holds is one the byte checks below know by name
         CHECK(device_buffers(h).size() == (size_t)g_made[DEV]);
-        if (debug) CHECK(nvx_enable_debug(h, 1) == NVX_OK && h->d_dphi);
-        if (debug == 2) CHECK(nvx_enable_debug(h, 0) == NVX_OK && !h->d_dphi);
+        const long dev0 = g_made[DEV];
+        if (debug) {
+            // the three debug buffers (delta-phi, |corr|, class sums) come and go together; asking twice makes nothing more
+            CHECK(nvx_enable_debug(h, 1) == NVX_OK && h->d_dphi && h->d_corr && h->d_csum);
+            CHECK(nvx_enable_debug(h, 1) == NVX_OK && g_made[DEV] == dev0 + 3);
+            CHECK(device_buffers(h).size() == (size_t)(g_made[DEV] - g_freed[DEV]));
+        }
+        if (debug == 2) {
+            CHECK(nvx_enable_debug(h, 0) == NVX_OK && !h->d_dphi && !h->d_corr && !h->d_csum && g_freed[DEV] == 3);
+            CHECK(nvx_enable_debug(h, 0) == NVX_OK && g_freed[DEV] == 3);
+        }
         g_order = true;
         nvx_destroy(h);
         g_order = false;
         for (int k = 0; k < NKIND; k++) CHECK(g_made[k] == g_freed[k] && g_made[k] > 0);
+        CHECK(outstanding() == 0);
+    }
+    // a failure at any of nvx_enable_debug's three buffers leaves none of them
+    for (int k = 1; k <= 3; k++) {
+        nvx_handle *h = create(c);
+        const long live0 = outstanding();
+        g_calls = 0; g_fail_at = k;
+        CHECK(nvx_enable_debug(h, 1) == NVX_ERR_NOMEM && !h->d_dphi && !h->d_corr && !h->d_csum && outstanding() == live0);
+        g_fail_at = 0;
+        nvx_destroy(h);
         CHECK(outstanding() == 0);
     }
     // (b) a failure at every creating call of nvx_create unwinds completely

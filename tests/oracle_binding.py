@@ -41,6 +41,7 @@ for name, res, args in [
     ("nvxo_mixer_table", None, [_vp, _vp]), ("nvxo_bitfilter_table", None, [_vp, _vp]),
     ("nvxo_decode", _sz, [_vp, _sz, _vp, _vp]), ("nvxo_decode_inject", _sz, [_vp, _sz, _vp, _sz, _i, C.POINTER(_i)]),
     ("nvxo_pipe_reinit", None, [_vp, _i]), ("nvxo_decode_with", _sz, [_vp, _sz, _vp, _vp, C.POINTER(_sz)]),
+    ("nvxo_decode_taps", _sz, [_vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("nvxo_sm_new", _vp, [_i, MSG_FN, _vp]), ("nvxo_sm_free", None, [_vp]), ("nvxo_sm_bit", None, [_vp, C.c_char]),
     ("nvxo_sm_trace", C.c_char_p, [_vp, C.POINTER(_sz)]),
     ("nvxo_pipe_new", _vp, [_i, _i, _i, MSG_FN, _vp]), ("nvxo_pipe_free", None, [_vp]),
@@ -144,6 +145,23 @@ def decode_with(y3: np.ndarray, atan2_fn_ptr) -> Tuple[str, int]:
     mism = _sz(0)
     n = L.nvxo_decode_with(_p(y3), y3.shape[0], bits, atan2_fn_ptr, C.byref(mism))
     return bits.raw[:n].decode("ascii"), mism.value
+
+
+def decode_taps(y3: np.ndarray, atan2_fn_ptr=None) -> Dict[str, object]:
+    """The decoder with its bit-timing filter tapped (nvxo_decode_taps), per 900 S/s sample: 'dphi', 'corr' (|corr|, NaN
+    before sample 8), 'csum' (class sum written there, NaN before 574), 'argmax' (int32: first maximum at a timing
+    evaluation, before the slew limiter; -1 elsewhere), 'bit_at' (uint8: 'B' / 'Y' where the FSM decided a bit -- the
+    last sample of its window -- else 0) and 'bits'.  atan2_fn_ptr: C function pointer, or None = libm."""
+    y3 = np.ascontiguousarray(y3, dtype=np.float64).reshape(-1, 2)
+    n3 = y3.shape[0]
+    bits = C.create_string_buffer(n3 + 1)
+    out = {k: np.empty(n3) for k in ("dphi", "corr", "csum")}
+    out["argmax"] = np.empty(n3, dtype=np.int32)
+    out["bit_at"] = np.empty(n3, dtype=np.uint8)
+    nb = L.nvxo_decode_taps(_p(y3), n3, bits, atan2_fn_ptr, _p(out["dphi"]), _p(out["corr"]), _p(out["csum"]), _p(out["argmax"]),
+                            _p(out["bit_at"]))
+    out["bits"] = bits.raw[:nb].decode("ascii")
+    return out
 
 
 def mixer_table() -> Tuple[np.ndarray, np.ndarray]:
@@ -279,7 +297,7 @@ def have_ref() -> bool:
 
 def run_ref(seam: str, data: bytes, probe: Tuple = (), ref_dir: Path | None = None) -> Dict[str, bytes]:
     """Run oracle/_ref/ref_<seam> on `data`; returns {output name: bytes, 'stdout': bytes}.
-    probe: ("reinit", n, which) for the full / bits seams, ("inject", n, value) for the decoder seam
+    probe: ("reinit", n, which) for the full / bits seams, ("inject", n, value) for the decoder seams
     (oracle/ref_seams/ref_harness.cpp); ref_dir: seams built elsewhere (another set of compiler flags)."""
     with tempfile.TemporaryDirectory() as td:
         inp = Path(td) / "in.bin"
@@ -289,6 +307,10 @@ def run_ref(seam: str, data: bytes, probe: Tuple = (), ref_dir: Path | None = No
         for f in Path(td).glob("o.*.bin"):
             out[f.name[2:-4]] = f.read_bytes()
         return out
+
+
+def have_ref_taps() -> bool:
+    return (REF / "ref_taps").exists()
 
 
 def have_ref_wav() -> bool:
