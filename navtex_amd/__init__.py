@@ -176,6 +176,17 @@ class HandleStats:
         N.check(lib.nvx_kernel_time_stats(self._h, which, C.byref(s), C.byref(n), int(reset)), "nvx_kernel_time_stats")
         return s.value, n.value
 
+    def enable_signal_report(self, on: bool = True) -> None:
+        """Per-chain signal reports on or off (nvx_enable_signal_report; off drops them)."""
+        N.check(lib.nvx_enable_signal_report(self._h, int(on)), "nvx_enable_signal_report")
+
+    def signal_report(self, stream: int = 0, chain: int = 0, reset: bool = False) -> dict:
+        """The signal report of decoded stream `stream`, chain 0 / 1 (nvx_signal_report_read): every field of
+        nvx_signal_report -- counts, raw sums and the derived power_db, b_hz, y_hz, offset_hz, shift_hz, eye_snr_db, contrast."""
+        r = N.SignalReport()
+        N.check(lib.nvx_signal_report_read(self._h, stream, chain, C.byref(r), int(reset)), "nvx_signal_report_read")
+        return {f: getattr(r, f) for f, _ in N.SignalReport._fields_}
+
 
 
 class Pipeline(HandleStats):
@@ -439,6 +450,18 @@ class Group:
         v = HandleStats()
         v._h = h
         return v
+
+    def enable_signal_report(self, on: bool = True) -> None:
+        """Signal reports on or off for every member (HandleStats.enable_signal_report)."""
+        for m in range(len(self.members)):
+            self.member_view(m).enable_signal_report(on)
+
+    def signal_report(self, stream: int, chain: int = 0, reset: bool = False) -> dict:
+        """The signal report of global stream `stream` (HandleStats.signal_report of the member that owns it)."""
+        m = self.member_of(stream)
+        if m < 0:
+            raise ValueError(f"stream {stream} is not in the group")
+        return self.member_view(m).signal_report(stream - self.members[m][1], chain, reset)
 
     def process_resident(self, ptrs: Sequence[int], pitch: int, first_frame: int, n_frames: int) -> None:
         arr = (C.c_void_p * len(ptrs))(*ptrs)

@@ -49,6 +49,13 @@ class SynthStream(C.Structure):
     _fields_ = [("seed", C.c_uint32), ("noise_amp", C.c_int32), ("n_carriers", C.c_int32), ("carrier", Carrier * 16)]
 
 
+class SignalReport(C.Structure):
+    """nvx_signal_report (include/navtex_amd_signal.h)."""
+    _fields_ = [("samples", C.c_uint64), ("b_samples", C.c_uint64)] + [(f, C.c_double) for f in (
+        "sum_power", "sum_dphi_b", "sum_dphi2_b", "sum_dphi_y", "sum_dphi2_y", "sum_mf_hi", "sum_mf_lo",
+        "power_db", "b_hz", "y_hz", "offset_hz", "shift_hz", "eye_snr_db", "contrast")]
+
+
 def _load() -> C.CDLL:
     if not _LIB_PATH.exists():
         raise ImportError(
@@ -95,6 +102,7 @@ def _load() -> C.CDLL:
         "nvx_kernel_time_stats": (i, [vp, i, C.POINTER(C.c_double), C.POINTER(C.c_uint64), i]),
         "nvx_debug_y3": (sz, [vp, i, i, vp, sz]), "nvx_debug_dphi": (sz, [vp, i, i, vp, sz]),
         "nvx_debug_timing": (sz, [vp, i, i, vp, vp, vp, sz]),
+        "nvx_enable_signal_report": (i, [vp, i]), "nvx_signal_report_read": (i, [vp, i, i, C.POINTER(SignalReport), i]),
         "nvx_device_count": (i, []), "nvx_device_alloc": (vp, [i, sz]), "nvx_device_free": (None, [i, vp]),
         "nvx_memcpy_h2d": (i, [i, vp, vp, sz]), "nvx_memcpy_d2h": (i, [i, vp, vp, sz]), "nvx_device_sync": (i, [i]),
         "nvx_stream_create": (vp, [i]), "nvx_stream_destroy": (None, [i, vp]),

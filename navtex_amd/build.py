@@ -56,7 +56,7 @@ def build_lib(force: bool = False) -> Path:
     from concurrent.futures import ThreadPoolExecutor
     hipcc = _hipcc()
     OBJ.mkdir(exist_ok=True)
-    headers = list(CSRC.glob("*.h")) + [ROOT / "include" / "navtex_amd.h", Path(__file__)]
+    headers = list(CSRC.glob("*.h")) + list((ROOT / "include").glob("*.h")) + [Path(__file__)]
     objs, jobs = [], []
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
@@ -92,7 +92,7 @@ def build_variant(name: str, flags, sources=("nvx_cascade.hip", "nvx_wideband_fu
     build_lib()
     out_dir = ROOT / "tests" / "_variants"
     out_dir.mkdir(exist_ok=True)
-    headers = list(CSRC.glob("*.h")) + [ROOT / "include" / "navtex_amd.h", Path(__file__)]
+    headers = list(CSRC.glob("*.h")) + list((ROOT / "include").glob("*.h")) + [Path(__file__)]
     objs, jobs = [], []
     for src in C_SOURCES + HIP_SOURCES + CXX_SOURCES:
         if src in sources:

@@ -8,6 +8,8 @@
 // (and the void reference-shaped entry points print and abort()).
 #include "nvx_handle.h"
 #include <chrono>
+#include <cmath>
+#include "navtex_amd_signal.h"
 #include "nvx_fsm.h"
 
 // ------------------------------------------------------------------ errors
@@ -102,6 +104,19 @@ static void free_debug(nvx_handle *h)
     for (double **p : { &h->d_dphi, &h->d_corr, &h->d_csum }) { (void)hipFree(*p); *p = nullptr; }
 }
 
+// nvx_enable_signal_report's buffers, made together and released together; what the reports had summed goes with them
+static void free_signal(nvx_handle *h)
+{
+    (void)hipFree(h->d_sig_part); h->d_sig_part = nullptr;
+    for (auto &r : h->res) {
+        (void)hipFree(r.d_sig); r.d_sig = nullptr;
+        (void)hipHostFree(r.h_sig); r.h_sig = nullptr;
+        r.sig = false;                                   // (a launch still to be collected brings no records any more)
+    }
+    for (auto &s : h->slots) s.sig = SigSums{};
+    h->sig_on = false; h->sig_stride = 0;
+}
+
 static void free_handle(nvx_handle *h)
 {
     if (!h) return;
@@ -110,6 +125,7 @@ static void free_handle(nvx_handle *h)
     (void)drain(h);
     snprintf(g_err, sizeof g_err, "%s", err.c_str());
     free_debug(h);
+    free_signal(h);
     for (auto it = h->made.rbegin(); it != h->made.rend(); ++it) {      // the streams, made first, go last
         switch (it->first) {
         case HipRes::stream: (void)hipStreamDestroy((hipStream_t)it->second); break;
@@ -287,6 +303,7 @@ static int clear_streams_locked(nvx_handle *h, int first, int last)
     for (int k = slot0; k < slot0 + n_sl; k++) {
         Slot &s = h->slots[k];
         s.bits.clear(); s.base = 0; s.polled = 0;
+        s.sig = SigSums{};
         if (s.sitor) nvx_sitor_reset(s.sitor);
     }
     const int64_t now = nvx_now_ns();
@@ -415,6 +432,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     da.state_i = h->d_di; da.fsm_table = h->d_fsm_tab; da.words = h->d_words;
     da.bits = r.d_bits; da.bits_cap = h->bits_cap; da.nbits = r.d_nbits; da.dphi = h->d_dphi; da.ties = h->d_ties;
     da.corr = h->d_corr; da.csum = h->d_csum;
+    da.sig = h->sig_on ? r.d_sig : nullptr; da.sig_part = h->d_sig_part; da.sig_stride = h->sig_stride;
 
     // cascade on `st`: it may not overwrite y3[yb] before the demodulator of two launches ago has read it
     if (h->demod_pending[yb]) HIP_TRY(hipStreamWaitEvent(st, h->demod_done[yb], 0));
@@ -471,6 +489,8 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     HIP_TRY(hipMemcpyAsync(h->h_ties, h->d_ties, sizeof(nvx_tie_stats), hipMemcpyDeviceToHost, sd));
     HIP_TRY(hipMemcpyAsync(r.h_nbits, r.d_nbits, (size_t)h->n_slots * sizeof(int), hipMemcpyDeviceToHost, sd));
     HIP_TRY(hipMemcpyAsync(r.h_bits, r.d_bits, (size_t)h->n_slots * h->bits_cap, hipMemcpyDeviceToHost, sd));
+    if (da.sig) HIP_TRY(hipMemcpyAsync(r.h_sig, r.d_sig, (size_t)h->n_slots * sizeof(nvx_sig_rec), hipMemcpyDeviceToHost, sd));
+    r.sig = da.sig != nullptr;
     HIP_TRY(hipEventRecord(r.done, sd));
     HIP_TRY(hipEventRecord(h->launch_done, sd));                    // sd has waited for st's last operation
     h->launch_done_valid = true; h->last_launch_stream = st;
@@ -593,6 +613,13 @@ int nvx_collect_locked(nvx_handle *h, uint64_t upto)
                     s.bits.resize(at + (size_t)n);
                     for (int b = 0; b < n; b++) s.bits[at + b] = ((pw[b >> 5] >> (b & 31)) & 1u) ? 'B' : 'Y';
                     if (s.sitor) nvx_sitor_receive_bits(s.sitor, s.bits.data() + at, (size_t)n);
+                    if (r.sig) {                                                // the signal report moves with the bits
+                        const nvx_sig_rec &q = r.h_sig[i];
+                        SigSums &g = s.sig;
+                        g.samples += q.samples; g.b_samples += q.b_samples;
+                        g.power += q.sum_power; g.dphi_b += q.sum_dphi_b; g.dphi2_b += q.sum_dphi2_b;
+                        g.dphi_y += q.sum_dphi_y; g.dphi2_y += q.sum_dphi2_y; g.hi += q.sum_mf_hi; g.lo += q.sum_mf_lo;
+                    }
                     if (s.bits.size() > 2 * h->bit_history) {                // a receiver runs for weeks: bound the poll history
                         const size_t drop = s.bits.size() - h->bit_history;
                         s.bits.erase(0, drop);
@@ -779,6 +806,74 @@ extern "C" int nvx_enable_debug(nvx_handle *h, int enabled)
         }
     }
     if (!enabled) free_debug(h);
+    return NVX_OK;
+}
+
+extern "C" int nvx_enable_signal_report(nvx_handle *h, int on)
+{
+    if (!h) { nvx_set_error("nvx_enable_signal_report: null handle"); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
+    if (!on) { free_signal(h); return NVX_OK; }
+    if (h->sig_on) return NVX_OK;
+    // partials per slot: one, or (the tile-parallel front) the head's and one per tile from the third on
+    const int tiles = (h->y3_cap + NVX_FRONT_TILE - 1) / NVX_FRONT_TILE;
+    const int stride = std::max(1, tiles - 1);
+    const size_t rec = (size_t)h->n_slots * sizeof(nvx_sig_rec);
+    hipError_t e = hipMalloc(&h->d_sig_part, rec * (size_t)stride);
+    for (auto &r : h->res) {
+        if (e == hipSuccess) e = hipMalloc(&r.d_sig, rec);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&r.h_sig, rec, hipHostMallocDefault);
+    }
+    if (e != hipSuccess) {
+        free_signal(h);
+        nvx_set_error("nvx_enable_signal_report: allocation failed: %s", hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? NVX_ERR_NOMEM : NVX_ERR_HIP;
+    }
+    h->sig_stride = stride;
+    h->sig_on = true;
+    return NVX_OK;
+}
+
+// the derived fields of navtex_amd_signal.h, in double; NaN where a denominator is 0
+static void signal_derive(nvx_signal_report *o)
+{
+    const double nan = std::nan(""), hz = 900.0 / (2.0 * M_PI);
+    const uint64_t ny = o->samples - o->b_samples;
+    o->power_db = o->samples ? 10.0 * std::log10(o->sum_power / (double)o->samples) : nan;
+    const double mb = o->b_samples ? o->sum_dphi_b / (double)o->b_samples : nan;
+    const double my = ny ? o->sum_dphi_y / (double)ny : nan;
+    o->b_hz = mb * hz; o->y_hz = my * hz;
+    o->offset_hz = (o->b_hz + o->y_hz) / 2.0;
+    o->shift_hz = o->b_hz - o->y_hz;
+    const double vb = std::max(0.0, o->sum_dphi2_b / (double)o->b_samples - mb * mb);
+    const double vy = std::max(0.0, o->sum_dphi2_y / (double)ny - my * my);
+    const double half = (mb - my) / 2.0, noise = (vb + vy) / 2.0;
+    o->eye_snr_db = (o->b_samples && ny && noise > 0.0) ? 10.0 * std::log10(half * half / noise) : nan;
+    const double mf = o->sum_mf_hi + o->sum_mf_lo;
+    o->contrast = mf != 0.0 ? (o->sum_mf_hi - o->sum_mf_lo) / mf : nan;
+}
+
+extern "C" int nvx_signal_report_read(nvx_handle *h, int stream, int chain, nvx_signal_report *out, int reset)
+{
+    if (!h || !out) { nvx_set_error("nvx_signal_report_read: null argument"); return NVX_ERR_ARG; }
+    if (stream < 0 || stream >= h->n_streams || chain < 0 || chain > 1) { nvx_set_error("nvx_signal_report_read: bad stream or chain"); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->poisoned) return nvx_poisoned_error(h);
+    if (!h->sig_on) { nvx_set_error("nvx_signal_report_read: signal reports are off (nvx_enable_signal_report)"); return NVX_ERR_STATE; }
+    if (h->collected != h->launched) {                   // what has finished, without waiting (nvx_poll)
+        HIP_TRY(hipSetDevice(h->cfg.device));
+        int rc = nvx_collect_ready_locked(h);
+        if (rc != NVX_OK) return rc;
+    }
+    SigSums &g = h->slots[2 * stream + chain].sig;
+    memset(out, 0, sizeof *out);
+    out->samples = g.samples; out->b_samples = g.b_samples;
+    out->sum_power = g.power; out->sum_dphi_b = g.dphi_b; out->sum_dphi2_b = g.dphi2_b;
+    out->sum_dphi_y = g.dphi_y; out->sum_dphi2_y = g.dphi2_y; out->sum_mf_hi = g.hi; out->sum_mf_lo = g.lo;
+    signal_derive(out);
+    if (reset) g = SigSums{};
     return NVX_OK;
 }
 

@@ -59,7 +59,7 @@ static_assert(DI_COUNT == NVX_DEMOD_INTS && DS_COUNT == NVX_DEMOD_DOUBLES && DI_
 #define NVX_FRONT_THREADS 128
 #endif
 #ifndef DTL
-#define DTL 432
+#define DTL NVX_FRONT_TILE
 static_assert(DTL % 9 == 0, "a tile is a whole number of bit periods");
 #endif
 #define FRONT_SLIDE ((567 + NVX_FRONT_THREADS - 1) / NVX_FRONT_THREADS)
@@ -85,7 +85,9 @@ __device__ __forceinline__ double front_dphi(double2 s, double2 p)
 }
 // mark/space decision for a window ENDING at sample t, decoder.C:115-132: float*float product, double*float product,
 // double sum, accumulate in double, round to float -- five samples, filter index 0..4
-__device__ __forceinline__ unsigned char front_decision(double2 w0, double2 w1, double2 w2, double2 w3, double2 w4)     // w_i = sample t - 4 + i
+// hi / lo: the larger and the smaller of the two energies compared (the signal report's matched-filter contrast)
+__device__ __forceinline__ unsigned char front_decision(double2 w0, double2 w1, double2 w2, double2 w3, double2 w4,       // w_i = sample t - 4 + i
+                                                        float &hi, float &lo)
 {
     float BR = 0.0f, BI = 0.0f, YR = 0.0f, YI = 0.0f;
 #pragma unroll
@@ -100,7 +102,62 @@ __device__ __forceinline__ unsigned char front_decision(double2 w0, double2 w1, 
     }
     const float Brot = BR * BR + BI * BI;
     const float Yrot = YR * YR + YI * YI;
-    return (Brot > Yrot) ? 1 : 0;
+    const bool b = Brot > Yrot;
+    hi = b ? Brot : Yrot; lo = b ? Yrot : Brot;
+    return b ? 1 : 0;
+}
+
+// ---- signal report (nvx_kernels.h, nvx_sig_rec): one thread's sums over the samples it owns, then the workgroup's in a
+// fixed order -- a butterfly within each wave (every lane ends with the same bits), the waves in index order.  Adds and
+// multiplies only: nothing here may become an FMA (the file is compiled with -ffp-contract=off).
+// (the count of samples is not summed: the publisher knows it)
+struct FrontSig { double power, dphi_b, dphi2_b, dphi_y, dphi2_y, hi, lo; unsigned nb, pad; };
+__device__ __forceinline__ void front_sig_init(FrontSig &s)
+{
+    s.power = s.dphi_b = s.dphi2_b = s.dphi_y = s.dphi2_y = s.hi = s.lo = 0.0; s.nb = s.pad = 0;
+}
+__device__ __forceinline__ void front_sig_add(FrontSig &s, double2 y, double ds, unsigned char d, float hi, float lo)
+{
+    s.power += y.x * y.x + y.y * y.y;
+    // the other class's sums gain +0.0: no change (a sum that starts at +0.0 never becomes -0.0), and no branch
+    const double b = d ? ds : 0.0, m = d ? 0.0 : ds;
+    s.dphi_b += b; s.dphi2_b += b * b; s.dphi_y += m; s.dphi2_y += m * m;
+    s.hi += (double)hi; s.lo += (double)lo; s.nb += d;
+}
+__device__ __forceinline__ double front_wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+__device__ __forceinline__ unsigned front_wave_sum(unsigned v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+// the workgroup's sums over its n counted samples -> partial record `rec` (every thread calls it; s_w: one FrontSig per wave
+// in LDS)
+__device__ __forceinline__ void front_sig_publish(FrontSig s, unsigned n, FrontSig *s_w, nvx_sig_rec *rec, int tid)
+{
+    s.power = front_wave_sum(s.power); s.dphi_b = front_wave_sum(s.dphi_b); s.dphi2_b = front_wave_sum(s.dphi2_b);
+    s.dphi_y = front_wave_sum(s.dphi_y); s.dphi2_y = front_wave_sum(s.dphi2_y); s.hi = front_wave_sum(s.hi); s.lo = front_wave_sum(s.lo);
+    s.nb = front_wave_sum(s.nb);
+    if ((tid & 63) == 0) s_w[tid >> 6] = s;
+    __syncthreads();
+    if (tid == 0) {
+        FrontSig t = s_w[0];
+#pragma unroll
+        for (int w = 1; w < NVX_FRONT_THREADS / 64; w++) {
+            const FrontSig &u = s_w[w];
+            t.power += u.power; t.dphi_b += u.dphi_b; t.dphi2_b += u.dphi2_b; t.dphi_y += u.dphi_y; t.dphi2_y += u.dphi2_y;
+            t.hi += u.hi; t.lo += u.lo; t.nb += u.nb;
+        }
+        nvx_sig_rec r;
+        r.sum_power = t.power; r.sum_dphi_b = t.dphi_b; r.sum_dphi2_b = t.dphi2_b; r.sum_dphi_y = t.dphi_y; r.sum_dphi2_y = t.dphi2_y;
+        r.sum_mf_hi = t.hi; r.sum_mf_lo = t.lo; r.samples = n; r.b_samples = t.nb;
+        *rec = r;
+    }
 }
 // transition correlator, decoder.C:157-177: mask[i] * dphi[g-8+i], i ascending; dp points at dphi of sample g-8
 __device__ __forceinline__ double front_corr(const double *dp)
@@ -201,7 +258,10 @@ struct FrontWalkLds {
     double C[567 + DTL];
     unsigned char D[DTL];
     unsigned near, evals, minm;
+    FrontSig sig[NVX_FRONT_THREADS / 64];
 };
+// SIG: the signal report's sums (a.sig != NULL).  A form of its own, so that without them the walk is the code it was.
+template <bool SIG>
 __device__ __forceinline__ void front_sequential(const nvx_demod_args &a, int chain_index, int n_tiles_here, FrontWalkLds &lds)
 {
     double *const s_dphi = lds.dphi, *const s_S = lds.S, *const s_C = lds.C;
@@ -213,6 +273,9 @@ __device__ __forceinline__ void front_sequential(const nvx_demod_args &a, int ch
     if (!a.slot_active[slot]) return;                    // uniform over the block
     if (tid == 0) { s_near = 0; s_evals = 0; s_minm = 0x7f800000u; }
     FrontTies ties = front_ties_init();
+    constexpr bool sig_on = SIG;
+    FrontSig sig;
+    front_sig_init(sig);
 
     const double *st = ch.st_rd;
     const double2 *y3 = a.y3 + (size_t)slot * a.y3_cap + a.y3_base;
@@ -236,7 +299,10 @@ __device__ __forceinline__ void front_sequential(const nvx_demod_args &a, int ch
             const double ds = front_dphi(w4, w3);
             s_dphi[8 + L] = ds;
             if (dphi_out) dphi_out[t] = ds;
-            s_D[L] = front_decision(y3_at(y3, hist, t - 4), y3_at(y3, hist, t - 3), y3_at(y3, hist, t - 2), w3, w4);
+            float hi, lo;
+            const unsigned char d = front_decision(y3_at(y3, hist, t - 4), y3_at(y3, hist, t - 3), y3_at(y3, hist, t - 2), w3, w4, hi, lo);
+            s_D[L] = d;
+            if (sig_on && gt + L >= G_DAB) front_sig_add(sig, w4, ds, d, hi, lo);
         }
         if (tid < 9 * tl9 - tl) s_D[tl + tid] = 0;       // a ragged last period: no window ends on samples the stream never had
         __syncthreads();
@@ -268,6 +334,10 @@ __device__ __forceinline__ void front_sequential(const nvx_demod_args &a, int ch
     }
 
     front_publish_ties(a, ties, &s_near, &s_evals, &s_minm, tid);
+    if (sig_on) {                                        // partial 0: the walk, or tiles 0-1; samples with g >= G_DAB
+        const unsigned skip = ch.g0 >= G_DAB ? 0u : (unsigned)min((unsigned long long)n_here, G_DAB - ch.g0);
+        front_sig_publish(sig, (unsigned)n_here - skip, lds.sig, a.sig_part + (size_t)slot * a.sig_stride, tid);
+    }
     if (n_tiles_here > 0) return;                        // the last tile of the tile-parallel form stores the state
     double *sw = ch.st_wr;
     if (tid < 4 && n3 >= 4) { const double2 l = y3[n3 - 4 + tid]; sw[DS_Y3 + 2 * tid] = l.x; sw[DS_Y3 + 2 * tid + 1] = l.y; }
@@ -275,10 +345,13 @@ __device__ __forceinline__ void front_sequential(const nvx_demod_args &a, int ch
     for (int i = tid; i < 567; i += NVX_FRONT_THREADS) sw[DS_C + i] = s_C[i];
 }
 
-__global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front(nvx_demod_args a)
+// Five waves per SIMD, as without the signal report's sums (95 VGPRs either way, no scratch): left to itself the compiler
+// spends 113 on them and the walk drops to four.  The head, few chains by construction, is left to itself.
+__global__ __launch_bounds__(NVX_FRONT_THREADS) __attribute__((amdgpu_waves_per_eu(5))) void nvx_demod_front(nvx_demod_args a)
 {
     __shared__ FrontWalkLds lds;
-    front_sequential(a, blockIdx.x, 0, lds);
+    if (a.sig) front_sequential<true>(a, blockIdx.x, 0, lds);
+    else front_sequential<false>(a, blockIdx.x, 0, lds);
 }
 
 // ---- form 2: tile-parallel (few chains, long launches: one channel replayed from a recording, BASELINE configs[1]) --
@@ -295,7 +368,8 @@ __global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front(nvx_demod_a
 __global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front_head(nvx_demod_args a)
 {
     __shared__ FrontWalkLds lds;
-    front_sequential(a, blockIdx.x, 2, lds);
+    if (a.sig) front_sequential<true>(a, blockIdx.x, 2, lds);
+    else front_sequential<false>(a, blockIdx.x, 2, lds);
 }
 __global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front_tiles(nvx_demod_args a, int wgs_per_chain)
 {
@@ -305,6 +379,7 @@ __global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front_tiles(nvx_d
     __shared__ double p_S[2 + DTL];                          // class sum of samples ta - 2 ..   (needs |corr| 566 back)
     __shared__ unsigned char p_D[DTL];
     __shared__ unsigned s_near, s_evals, s_minm;
+    __shared__ FrontSig s_sig[NVX_FRONT_THREADS / 64];
     const int tid = threadIdx.x;
     const FrontChain ch = front_chain(a, chain_index);
     const int slot = ch.slot;
@@ -318,6 +393,9 @@ __global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front_tiles(nvx_d
     double *corr_out = a.corr ? a.corr + (size_t)slot * a.y3_cap + a.y3_base : nullptr;
     double *csum_out = a.csum ? a.csum + (size_t)slot * a.y3_cap + a.y3_base : nullptr;
     const unsigned long long g_ta = ch.g0 + (unsigned long long)ta;
+    const bool sig_on = a.sig != nullptr;
+    FrontSig sig;                                            // the tile's own samples (g >= 864: all counted), never its look-back
+    front_sig_init(sig);
 
     for (int i = tid; i < FRONT_LOOKBACK + tl; i += NVX_FRONT_THREADS) {
         const int t = ta - FRONT_LOOKBACK + i;
@@ -325,7 +403,10 @@ __global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front_tiles(nvx_d
         p_dphi[i] = ds;
         if (i >= FRONT_LOOKBACK) {
             if (dphi_out) dphi_out[t] = ds;
-            p_D[i - FRONT_LOOKBACK] = front_decision(y3[t - 4], y3[t - 3], y3[t - 2], y3[t - 1], y3[t]);      // t - 4 >= 0: no history needed
+            float hi, lo;
+            const unsigned char d = front_decision(y3[t - 4], y3[t - 3], y3[t - 2], y3[t - 1], y3[t], hi, lo);      // t - 4 >= 0: no history needed
+            p_D[i - FRONT_LOOKBACK] = d;
+            if (sig_on) front_sig_add(sig, y3[t], ds, d, hi, lo);
         }
     }
     __syncthreads();
@@ -345,6 +426,7 @@ __global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front_tiles(nvx_d
     for (int M = tid; M < tl / 9; M += NVX_FRONT_THREADS)
         a.words[(size_t)slot * (a.y3_cap / 9) + (ta / 9 + M)] = front_word(&p_D[9 * M], &p_S[9 * M], g_ta + 9 * M + (G_CSA % 9) >= G_CSA, ties);
     front_publish_ties(a, ties, &s_near, &s_evals, &s_minm, tid);
+    if (sig_on) front_sig_publish(sig, (unsigned)tl, s_sig, a.sig_part + (size_t)slot * a.sig_stride + 1 + wg, tid);     // partial 1 + wg: tile 2 + wg
     if (ta + tl >= a.n3) {
         // ---- the last tile: what the next launch carries
         double *sw = ch.st_wr;
@@ -444,9 +526,21 @@ __global__ __launch_bounds__(64) void nvx_demod_fsm(nvx_demod_args a)
     SI(DI_SYNCED) = synced; SI(DI_SYNC_OFF) = synced ? r.so : 0; SI(DI_NEXT_SYNC_OFF) = r.nso;
     SI(DI_PHASE) = r.phase1 - 1; SI(DI_PREV_OFFSET) = r.prev_offset;
 #undef SI
+    if (a.sig) {                                         // the signal report: the front's partials of the chain, in tile order
+        const nvx_sig_rec *p = a.sig_part + (size_t)slot * a.sig_stride;
+        nvx_sig_rec s = p[0];
+        for (int k = 1; k < a.sig_parts; k++) {
+            const nvx_sig_rec &q = p[k];
+            s.sum_power += q.sum_power; s.sum_dphi_b += q.sum_dphi_b; s.sum_dphi2_b += q.sum_dphi2_b;
+            s.sum_dphi_y += q.sum_dphi_y; s.sum_dphi2_y += q.sum_dphi2_y; s.sum_mf_hi += q.sum_mf_hi; s.sum_mf_lo += q.sum_mf_lo;
+            s.samples += q.samples; s.b_samples += q.b_samples;
+        }
+        a.sig[slot] = s;
+    }
 }
 
-extern "C" hipError_t nvx_launch_demod_front(const nvx_demod_args *a, hipStream_t s)
+// Which form of the front a launch takes: the number of tile workgroups per chain (the tile-parallel form), or 0 (the walk)
+static int front_tile_wgs(const nvx_demod_args *a)
 {
     const unsigned chains = a->part ? (unsigned)(2 * a->per_part * a->n_part) : (unsigned)a->n_slots;
     // Few chains and a long launch: one workgroup per tile instead of one per chain (NVX_DEMOD_TILES=0/1 forces the
@@ -460,8 +554,15 @@ extern "C" hipError_t nvx_launch_demod_front(const nvx_demod_args *a, hipStream_
     const long long chain_frames = (long long)chains * (a->n3 / NVX_Y3_PER_FRAME);
     // (the tile form works on a.n3: every chain whole frames.  A launch that ends streams is one frame long: the walk.)
     const bool parallel = tiles >= 3 && (force >= 0 ? force != 0 : chain_frames <= 2560);
-    if (parallel) {
-        const int wgs = tiles - 2;                           // one workgroup per tile from the third on; the head walks the first two
+    return parallel ? tiles - 2 : 0;                         // one workgroup per tile from the third on; the head walks the first two
+}
+
+extern "C" hipError_t nvx_launch_demod_front(const nvx_demod_args *a, hipStream_t s)
+{
+    const unsigned chains = a->part ? (unsigned)(2 * a->per_part * a->n_part) : (unsigned)a->n_slots;
+    const int wgs = front_tile_wgs(a);
+    if (a->sig && 1 + wgs > a->sig_stride) return hipErrorInvalidValue;      // the partials would not fit their buffer
+    if (wgs) {
         hipLaunchKernelGGL(nvx_demod_front_head, dim3(chains), dim3(NVX_FRONT_THREADS), 0, s, *a);
         hipLaunchKernelGGL(nvx_demod_front_tiles, dim3(chains * (unsigned)wgs), dim3(NVX_FRONT_THREADS), 0, s, *a, wgs);
     } else {
@@ -473,7 +574,9 @@ extern "C" hipError_t nvx_launch_demod_front(const nvx_demod_args *a, hipStream_
 extern "C" hipError_t nvx_launch_demod_fsm(const nvx_demod_args *a, hipStream_t s)
 {
     const int chains = a->part ? 2 * a->per_part * a->n_part : a->n_slots;
-    hipLaunchKernelGGL(nvx_demod_fsm, dim3((unsigned)((chains + 63) / 64)), dim3(64), 0, s, *a);
+    nvx_demod_args b = *a;
+    b.sig_parts = 1 + front_tile_wgs(a);                 // as nvx_launch_demod_front chose
+    hipLaunchKernelGGL(nvx_demod_fsm, dim3((unsigned)((chains + 63) / 64)), dim3(64), 0, s, b);
     return hipGetLastError();
 }
 

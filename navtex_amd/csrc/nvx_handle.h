@@ -45,6 +45,11 @@ static const int RESULT_SLOTS = 4;
 
 struct Message { std::string bbbb, text; int freq; };
 
+struct SigSums {                       // a chain's signal report (navtex_amd_signal.h): counts and raw sums, folded launch by launch
+    uint64_t samples = 0, b_samples = 0;
+    double power = 0.0, dphi_b = 0.0, dphi2_b = 0.0, dphi_y = 0.0, dphi2_y = 0.0, hi = 0.0, lo = 0.0;
+};
+
 struct Slot {                          // one (stream, chain)
     bool active = false;
     int label = 0;
@@ -53,6 +58,7 @@ struct Slot {                          // one (stream, chain)
     size_t polled = 0;                 // nvx_poll_bits cursor, absolute
     nvx_sitor *sitor = nullptr;
     std::vector<Message> outbox;       // messages completed during a (possibly threaded) collect
+    SigSums sig;                       // signal report over the collected launches (while reports are on)
 };
 
 struct Result {                        // one in-flight launch's bit output
@@ -69,6 +75,9 @@ struct Result {                        // one in-flight launch's bit output
     hipEvent_t ev[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };   // begin/end of cascade, demod front, demod FSM, nvx_fir3
     bool timed = false;
     bool pending = false;
+    // signal reports (nvx_enable_signal_report): the launch's record per slot, device and pinned; sig = the launch carried them
+    nvx_sig_rec *d_sig = nullptr, *h_sig = nullptr;
+    bool sig = false;
 };
 
 // Decode latency of the live path (r4).  The reference decodes synchronously, sample by sample, and calls add_message
@@ -144,6 +153,11 @@ struct nvx_handle {
     double *d_dd[2] = { nullptr, nullptr };   // demodulator state blocks: a chain reads [its stream's parity], writes the other
     double *d_dphi = nullptr;          // nvx_enable_debug's buffers: not on the release list (made and freed there)
     double *d_corr = nullptr, *d_csum = nullptr;
+    // nvx_enable_signal_report's buffers, made and freed there as the debug buffers are (and by free_handle): the front's
+    // partial records [n_slots][sig_stride] and Result::d_sig / h_sig
+    bool sig_on = false;
+    nvx_sig_rec *d_sig_part = nullptr;
+    int sig_stride = 0;
     int *d_di = nullptr;
     uint32_t *d_fsm_tab = nullptr;     // bit-period transition table of the demodulator FSM (nvx_fsm.h)
     unsigned short *d_words = nullptr;

@@ -138,6 +138,19 @@ typedef struct {
     unsigned int pad;
 } nvx_tie_stats;
 
+/* Signal report of one chain over one launch (navtex_amd_signal.h): sums over its 900 S/s samples with g >= 8 (g = index
+ * since reset).  Per sample: P = I*I + Q*Q of y3, delta-phi, the decision d of the five-sample window ENDING there and
+ * hi / lo = max / min of that window's mark and space energies (float, widened).  64 bytes.                         */
+typedef struct {
+    double sum_power;                  /* sum P                                                  */
+    double sum_dphi_b, sum_dphi2_b;    /* sum delta-phi, sum delta-phi^2 over samples with d = 1 */
+    double sum_dphi_y, sum_dphi2_y;    /* ... with d = 0                                         */
+    double sum_mf_hi, sum_mf_lo;       /* sum hi, sum lo                                         */
+    unsigned samples, b_samples;       /* samples counted, of them with d = 1                    */
+} nvx_sig_rec;
+/* the front's time tile (nvx_demod.hip DTL): the tile form writes a partial record per tile from the third on */
+#define NVX_FRONT_TILE 432
+
 typedef struct {
     const double2 *y3;
     size_t y3_cap, y3_base;
@@ -158,6 +171,10 @@ typedef struct {
     double *corr, *csum;       /* optional debug taps of the bit-timing filter: |corr| and the class sum of every sample, */
                                /* same layout as y3 (or NULL; set together with dphi)                                     */
     nvx_tie_stats *ties;       /* cumulative arg-max margin statistics (never NULL)    */
+    nvx_sig_rec *sig;          /* signal reports on: [n_slots] records of this launch, folded by nvx_demod_fsm; NULL = off */
+    nvx_sig_rec *sig_part;     /* [n_slots][sig_stride] partial records of the front's workgroups, in tile order          */
+    int sig_stride;            /* partials per slot the buffer holds (the launcher refuses a launch that needs more)       */
+    int sig_parts;             /* set by the launchers: partials per slot this launch writes (1 = the walk)                */
 } nvx_demod_args;
 
 typedef struct {
