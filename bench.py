@@ -19,21 +19,29 @@ before touching torch or the GPU, and relays the child's line and exit status.
 Under a launcher (the driver's `python -m torch.distributed.run ... bench.py
 --gpus N`) it is simply one of the ranks.
 
-Every rank checks its OWN shard against the oracle before the timed region (all
-streams at N = 1, a spread sample of them per rank otherwise) AND after it: the
-bits the handle has accumulated over the warm-up and the timed launches -- the
-launches that were measured, with their state carried launch to launch --
-against the oracle fed the same frames as many times (`parity_after_timed`).
+A plain run does what the headline figure needs and nothing else: it sets up,
+warms up, times the steps, writes --dump-outputs if asked and prints the line.
+The launches and fetches it makes on the GPU are those of a --full run; it only
+leaves out the host-side checks and the side legs below.
+
+`--full` adds the checks and the other measurements, all outside the timed
+region.  Every rank checks its OWN shard against the oracle before the timed
+region (all streams at N = 1, a spread sample of them per rank otherwise) AND
+after it: the bits the handle has accumulated over the warm-up and the timed
+launches -- the launches that were measured, with their state carried launch to
+launch -- against the oracle fed the same frames as many times
+(`parity_after_timed`).
 The line's `parity` is the minimum over ranks of both, and a failed parity makes
 the process exit with status 3 after printing the line.
 
-At N = 1 the default line also carries, each outside the headline's timed
-region and each with its own parity checks (first launch and last):
+At N = 1 the --full line also carries the CPU baseline and, each with its own
+parity checks (first launch and last):
 `stage0_third_order`, `push_path` (host-fed streaming through nvx_push_iq,
 PCIe-inclusive), `live_latency` (two capture rings fed at the real rate),
 `variant_a` (the 252 kS/s cascade kernel) and `wideband` (the fused channeliser
 + cascade kernel).  A leg that raises is named in `legs_failed` and the process
 exits with status 4 after printing the line (--allow-leg-errors: status 0).
+The options that shape these checks and legs are refused without --full.
 
 `python bench.py --gpus N --group` runs the same workload through ONE process
 and the library's own multi-GPU object (nvx_group: one handle + host thread per
@@ -93,7 +101,7 @@ def parse():
                          "(nvx_config.stage0_order = 3: 76 dB of alias rejection instead of 25)")
     ap.add_argument("--no-stage0-extra", action="store_true", help="skip the third-order stage 0 measurement beside the headline (N = 1)")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the side legs of the default line (N = 1): variant_a, wideband, push_path (each a few seconds, outside the timed region)")
+                    help="skip the side legs of the --full line (N = 1): variant_a, wideband, push_path (each a few seconds, outside the timed region)")
     ap.add_argument("--allow-leg-errors", action="store_true", help="a side leg that raises is recorded but does not fail the run (default: exit status 4)")
     ap.add_argument("--after-timed", type=int, default=64, metavar="N",
                     help="streams per rank whose accumulated bits are checked against the oracle AFTER the timed region (at least 32 per rank)")
@@ -107,7 +115,18 @@ def parse():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what they computed for a fixed sample of rank 0's streams as DIR/<name>.npy "
                          "(float32/float64, at most 64 MB): the last step's fp64 cascade output and the bits decoded over the timed steps")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the oracle's parity checks before and after the timed region, the CPU baseline and, "
+                         "at N = 1, the side legs (a plain run times the same launches and checks nothing)")
+    args = ap.parse_args()
+    given = [f"--{d.replace('_', '-')}" for d in FULL_ONLY if getattr(args, d) != ap.get_default(d)]
+    if given and not args.full:
+        ap.error(f"{' '.join(given)} shape{'s' if len(given) == 1 else ''} what --full adds; a plain run has no checks or side legs")
+    return args
+
+
+# the options that only shape what --full adds (checks, CPU baseline, side legs)
+FULL_ONLY = ("cpu_streams", "no_cpu", "verify", "no_stage0_extra", "no_legs", "allow_leg_errors", "after_timed", "cic3_verify")
 
 
 DUMP_BUDGET = 64 << 20          # bytes, all files of --dump-outputs together
@@ -146,7 +165,6 @@ def dump_outputs(out_dir, nv, pipe, ids, bits_before):
 
 def run_wideband(args, nv, signals, ranks, rank, world, device, place):
     """Channeliser + 252 kS/s pipeline on W wideband streams per GPU."""
-    import oracle_binding as ob
     W, F = args.wideband, args.frames
     n_raw, n_sub = F * nv.FRAME_RAW, F * nv.FRAME_IN
     t0 = time.time()
@@ -159,27 +177,29 @@ def run_wideband(args, nv, signals, ranks, rank, world, device, place):
     def step():
         pipe.process_resident(raw, n_raw, 0, F)
 
-    # ---- parity: every rank checks its own shard against the oracle chain (channeliser restatement -> 8 two-chain
-    # pipelines): ALL wideband streams (16 carriers each) at N = 1, the first few otherwise
     ncpu = place["threads"]
-    nw = W if (world == 1 and args.verify < 0) else min(W, max(2, (args.verify if args.verify > 0 else 32) // 16))
     step(); pipe.fetch()
-    ok, sN, sample = True, 0.0, None
-    for w0 in range(0, nw, 32):
-        m = min(32, nw - w0)
-        part = raw.download(m * n_raw * 4, offset=w0 * n_raw * 4, dtype=np.int16).reshape(m, n_raw, 2)
-        secs, cpu_bits = ob.bench_wide(part, m, n_sub, ncpu, want_bits=True)
-        gpu_bits = [pipe.bits(s, c) for s in range(8 * w0, 8 * (w0 + m)) for c in (0, 1)]
-        ok = ok and gpu_bits == cpu_bits and all(len(b) > 0 for b in cpu_bits)
-        if sample is None:
-            sample, sN = part[: min(m, max(2, ncpu // 4))], secs * min(m, max(2, ncpu // 4)) / m
-    if not ok:
-        print(f"PARITY FAILURE (wideband, rank {rank}): GPU bits differ from the CPU oracle", file=sys.stderr)
-    parity = ranks.reduce(1.0 if ok else 0.0, "min") > 0.5
-    checked = int(ranks.reduce(16.0 * nw, "sum"))
-    near_ties = int(ranks.reduce(float(pipe.tie_stats()[0]), "sum"))
-    cpu = None
-    if rank == 0 and not args.no_cpu and world == 1:
+    parity, cpu = True, None
+    if args.full:
+        # ---- parity: every rank checks its own shard against the oracle chain (channeliser restatement -> 8 two-chain
+        # pipelines): ALL wideband streams (16 carriers each) at N = 1, the first few otherwise
+        import oracle_binding as ob
+        nw = W if (world == 1 and args.verify < 0) else min(W, max(2, (args.verify if args.verify > 0 else 32) // 16))
+        ok, sN, sample = True, 0.0, None
+        for w0 in range(0, nw, 32):
+            m = min(32, nw - w0)
+            part = raw.download(m * n_raw * 4, offset=w0 * n_raw * 4, dtype=np.int16).reshape(m, n_raw, 2)
+            secs, cpu_bits = ob.bench_wide(part, m, n_sub, ncpu, want_bits=True)
+            gpu_bits = [pipe.bits(s, c) for s in range(8 * w0, 8 * (w0 + m)) for c in (0, 1)]
+            ok = ok and gpu_bits == cpu_bits and all(len(b) > 0 for b in cpu_bits)
+            if sample is None:
+                sample, sN = part[: min(m, max(2, ncpu // 4))], secs * min(m, max(2, ncpu // 4)) / m
+        if not ok:
+            print(f"PARITY FAILURE (wideband, rank {rank}): GPU bits differ from the CPU oracle", file=sys.stderr)
+        parity = ranks.reduce(1.0 if ok else 0.0, "min") > 0.5
+        checked = int(ranks.reduce(16.0 * nw, "sum"))
+        near_ties = int(ranks.reduce(float(pipe.tie_stats()[0]), "sum"))
+    if args.full and rank == 0 and not args.no_cpu and world == 1:
         ns = sample.shape[0]
         rep = max(1, int(5.0 / max(sN, 1e-3)))
         sN = ob.bench_wide(sample, ns, n_sub, ncpu, repeat=rep)[0]
@@ -202,16 +222,17 @@ def run_wideband(args, nv, signals, ranks, rank, world, device, place):
     own_elapsed = time.perf_counter() - t0
     ranks.sync()
     elapsed = ranks.reduce(time.perf_counter() - t0, "max")
-    # ---- parity AFTER the timed region, as in the headline mode: the first wideband streams' 16 carriers each, everything
-    # decoded over warm-up + timed launches (channeliser halo, filter and demodulator state carried) against the oracle's replay
-    nw_after = min(W, 8)
-    part_after = raw.download(nw_after * n_raw * 4, dtype=np.int16).reshape(nw_after, n_raw, 2)
-    _secs, want_after = ob.replay_wide(part_after, nw_after, n_sub, ncpu, args.warmup + args.steps)
-    ok_after = [pipe.bits(s, c) for s in range(8 * nw_after) for c in (0, 1)] == want_after and all(len(b) > 0 for b in want_after)
-    if not ok_after:
-        print(f"PARITY FAILURE AFTER THE TIMED REGION (wideband, rank {rank}): GPU bits differ from the CPU oracle's replay", file=sys.stderr)
-    parity_after = ranks.reduce(1.0 if ok_after else 0.0, "min") > 0.5
-    parity = parity and parity_after
+    if args.full:
+        # ---- parity AFTER the timed region, as in the headline mode: the first wideband streams' 16 carriers each, everything
+        # decoded over warm-up + timed launches (channeliser halo, filter and demodulator state carried) against the oracle's replay
+        nw_after = min(W, 8)
+        part_after = raw.download(nw_after * n_raw * 4, dtype=np.int16).reshape(nw_after, n_raw, 2)
+        _secs, want_after = ob.replay_wide(part_after, nw_after, n_sub, ncpu, args.warmup + args.steps)
+        ok_after = [pipe.bits(s, c) for s in range(8 * nw_after) for c in (0, 1)] == want_after and all(len(b) > 0 for b in want_after)
+        if not ok_after:
+            print(f"PARITY FAILURE AFTER THE TIMED REGION (wideband, rank {rank}): GPU bits differ from the CPU oracle's replay", file=sys.stderr)
+        parity_after = ranks.reduce(1.0 if ok_after else 0.0, "min") > 0.5
+        parity = parity and parity_after
     stale, seal_failures, _ = pipe.integrity_stats()
     stale_all, seal_failures_all = int(ranks.reduce(float(stale), "sum")), int(ranks.reduce(float(seal_failures), "sum"))
     casc_ms, n_l = pipe.kernel_time_stats(0)
@@ -246,12 +267,14 @@ def run_wideband(args, nv, signals, ranks, rank, world, device, place):
                      "note": "exact mul-then-add fp64 (no FMA): the roof is the fp64 issue rate at 2.4 GHz, 256 CUs x 4 SIMDs x 16 lanes; "
                              "only the cascade's fp64 operations are counted, the channeliser's integer work rides on top"},
         "form": "fused (one kernel, sub-bands stay in LDS)",
-        "cpu_baseline": cpu, "parity": parity, "parity_streams_checked": checked, "parity_after_timed": parity_after,
-        "parity_after_timed_streams": int(ranks.reduce(16.0 * nw_after, "sum")), "parity_after_timed_launches": args.warmup + args.steps,
-        "demod": {"near_ties": near_ties},
+        "full": args.full,
         "host_threads": place["threads"], "placement": place, "gen_seconds": round(t_gen, 1),
-        "ranks": ranks.describe(own_elapsed / args.steps * 1e3, 16 * nw, casc_avg, device),
+        "ranks": ranks.describe(own_elapsed / args.steps * 1e3, 16 * nw if args.full else 0, casc_avg, device),
     }
+    if args.full:
+        line.update({"cpu_baseline": cpu, "parity": parity, "parity_streams_checked": checked, "parity_after_timed": parity_after,
+                     "parity_after_timed_streams": int(ranks.reduce(16.0 * nw_after, "sum")), "parity_after_timed_launches": args.warmup + args.steps,
+                     "demod": {"near_ties": near_ties}})
     pipe.close(); raw.free()
     finish(line, parity, ranks, rank)
 
@@ -268,8 +291,6 @@ def run_group(args):
     threads = int(os.environ.get("NVX_CPU_THREADS", max(1, min(16 * n, len(have)))))
     import navtex_amd as nv
     import signals
-    import oracle_binding as ob
-    import fullsize
     import gc
     gc.collect(); gc.freeze()
     if nv.device_count() <= max(devs):
@@ -301,12 +322,15 @@ def run_group(args):
 
     # ---- parity gate, every member its own shard: first launch from reset ...
     step(); group.fetch()
-    n_verify = args.verify if args.verify > 0 else (S if n == 1 else 32)
-    checked_m, bad_all, verify_s = [], [], 0.0
-    for m, (dev, first, count) in enumerate(group.members):
-        ids = fullsize.spread(S, n_verify)
-        c, bad, secs = fullsize.verify_streams(ob, bufs[m], pitch, n_per_stream, oraw, lambda s, f=first: group.bits(f + s, 0), ids, threads)
-        checked_m.append(c); bad_all += [first + b for b in bad]; verify_s += secs
+    if args.full:
+        import oracle_binding as ob
+        import fullsize
+        n_verify = args.verify if args.verify > 0 else (S if n == 1 else 32)
+        checked_m, bad_all, verify_s = [], [], 0.0
+        for m, (dev, first, count) in enumerate(group.members):
+            ids = fullsize.spread(S, n_verify)
+            c, bad, secs = fullsize.verify_streams(ob, bufs[m], pitch, n_per_stream, oraw, lambda s, f=first: group.bits(f + s, 0), ids, threads)
+            checked_m.append(c); bad_all += [first + b for b in bad]; verify_s += secs
     group.reset()
     for _ in range(args.warmup):
         step()
@@ -320,15 +344,17 @@ def run_group(args):
     elapsed = time.perf_counter() - t0
     # ... and after the timed region: what the measured launches produced (state carried launch to launch)
     loops = args.warmup + args.steps
-    after_m, bad_after, after_s = [], [], 0.0
-    for m, (dev, first, count) in enumerate(group.members):
-        ids = fullsize.spread(S, min(S, max(32, args.after_timed)))
-        c, bad, secs = fullsize.verify_replay(ob, bufs[m], pitch, n_per_stream, oraw, lambda s, f=first: group.bits(f + s, 0), ids, threads, loops,
-                                              gpu_count=lambda s, f=first: group.bit_count(f + s, 0))
-        after_m.append(c); bad_after += [first + b for b in bad]; after_s += secs
-    if bad_all or bad_after:
-        print(f"PARITY FAILURE (group): first launch {len(bad_all)} streams differ (first {bad_all[:8]}), after the timed region {len(bad_after)} (first {bad_after[:8]})", file=sys.stderr)
-    parity = not bad_all and not bad_after
+    parity = True
+    if args.full:
+        after_m, bad_after, after_s = [], [], 0.0
+        for m, (dev, first, count) in enumerate(group.members):
+            ids = fullsize.spread(S, min(S, max(32, args.after_timed)))
+            c, bad, secs = fullsize.verify_replay(ob, bufs[m], pitch, n_per_stream, oraw, lambda s, f=first: group.bits(f + s, 0), ids, threads, loops,
+                                                  gpu_count=lambda s, f=first: group.bit_count(f + s, 0))
+            after_m.append(c); bad_after += [first + b for b in bad]; after_s += secs
+        if bad_all or bad_after:
+            print(f"PARITY FAILURE (group): first launch {len(bad_all)} streams differ (first {bad_all[:8]}), after the timed region {len(bad_after)} (first {bad_after[:8]})", file=sys.stderr)
+        parity = not bad_all and not bad_after
     casc = []
     stale = failures = 0
     w_units = w_launches = 0
@@ -351,19 +377,22 @@ def run_group(args):
                      "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None, "traffic": traffic, "traffic_source": traffic_source,
                      "algorithmic_bytes_per_launch": bytes_per_step, "avg_launch_ms": round(casc_avg, 3), "per_device": "slowest member; ranks.cascade_avg_launch_ms_per_rank has all",
                      "handoff": {"units_waited_frac": round(w_units / max(1, w_launches * S * F), 4), "stale_detected": stale, "launches_failed_integrity": failures}},
-        "cpu_baseline": None,
-        "parity": parity, "parity_streams_checked": sum(checked_m), "parity_seconds": round(verify_s, 1),
-        "parity_after_timed": not bad_after, "parity_after_timed_streams": sum(after_m), "parity_after_timed_launches": loops, "parity_after_timed_seconds": round(after_s, 1),
+        "full": args.full,
         "host_threads": threads,
         "ranks": {"world_size_seen": n, "backend": "group", "note": "one process; a 'rank' here is a member handle of the nvx_group (its own device, host thread and result ring)",
                   "ms_per_step_per_rank": [round(elapsed / args.steps * 1e3, 3)] * n, "ms_per_step_min": round(elapsed / args.steps * 1e3, 3),
                   "ms_per_step_max": round(elapsed / args.steps * 1e3, 3),
-                  "parity_streams_checked_per_rank": checked_m, "parity_after_timed_streams_per_rank": after_m,
                   "cascade_avg_launch_ms_per_rank": [round(c, 3) for c in casc], "device_per_rank": [d for d, _, _ in group.members],
                   "first_stream_per_rank": [f for _, f, _ in group.members]},
         "hbm_gbs_whole_job": round(n * bytes_per_step * args.steps / elapsed / 1e9, 1), "gen_seconds": round(t_gen, 1),
         "messages_delivered": len(group.messages),
     }
+    if args.full:
+        line.update({"cpu_baseline": None,
+                     "parity": parity, "parity_streams_checked": sum(checked_m), "parity_seconds": round(verify_s, 1),
+                     "parity_after_timed": not bad_after, "parity_after_timed_streams": sum(after_m), "parity_after_timed_launches": loops,
+                     "parity_after_timed_seconds": round(after_s, 1)})
+        line["ranks"].update({"parity_streams_checked_per_rank": checked_m, "parity_after_timed_streams_per_rank": after_m})
     group.close()
     for b in bufs:
         b.free()
@@ -435,8 +464,9 @@ def main():
     if args.wideband:
         run_wideband(args, nv, signals, ranks, rank, world, device, place)
         return
-    import oracle_binding as ob
-    import fullsize
+    if args.full:
+        import oracle_binding as ob
+        import fullsize
     S, F = args.streams, args.frames
     raw = not args.variant_a
     order = 3 if (raw and args.stage0 == "cic3") else 1
@@ -465,25 +495,28 @@ def main():
                        bit_history=max(65536, (args.warmup + args.steps + 1) * F * 32 + 4096))
     ncpu = place["threads"]
 
-    # ---- parity gate: EVERY rank checks its own shard against the oracle, from reset state -----------------------
+    # ---- one launch from reset, then a reset: a plain run makes it too, so both kinds of run time the same launches ------
     pipe.process_resident(buf, pitch, 0, F)
     pipe.fetch()
-    n_verify = args.verify if args.verify > 0 else (S if world == 1 else 32)
-    ids = fullsize.spread(S, n_verify)
-    checked, bad, verify_s = fullsize.verify_streams(ob, buf, pitch, n_per_stream, oraw, lambda s: pipe.bits(s, 0), ids, ncpu)
-    if bad:
-        print(f"PARITY FAILURE (rank {rank}): {len(bad)} of {checked} streams differ from the CPU oracle, first {bad[:8]}", file=sys.stderr)
-    parity = ranks.reduce(0.0 if bad else 1.0, "min") > 0.5
-    checked_all = int(ranks.reduce(float(checked), "sum"))
-    near, evals, margin = pipe.tie_stats()
-    near_all = int(ranks.reduce(float(near), "sum"))
-    margin_all = ranks.reduce(margin if evals else 1.0, "min")
+    checked, parity = 0, True
+    if args.full:
+        # ---- parity gate: EVERY rank checks its own shard against the oracle, from reset state -----------------------
+        n_verify = args.verify if args.verify > 0 else (S if world == 1 else 32)
+        ids = fullsize.spread(S, n_verify)
+        checked, bad, verify_s = fullsize.verify_streams(ob, buf, pitch, n_per_stream, oraw, lambda s: pipe.bits(s, 0), ids, ncpu)
+        if bad:
+            print(f"PARITY FAILURE (rank {rank}): {len(bad)} of {checked} streams differ from the CPU oracle, first {bad[:8]}", file=sys.stderr)
+        parity = ranks.reduce(0.0 if bad else 1.0, "min") > 0.5
+        checked_all = int(ranks.reduce(float(checked), "sum"))
+        near, evals, margin = pipe.tie_stats()
+        near_all = int(ranks.reduce(float(near), "sum"))
+        margin_all = ranks.reduce(margin if evals else 1.0, "min")
 
-    # ---- CPU baseline (rank 0, N = 1 leg of the contract; BASELINE.md 3: one thread AND all physical cores) -------
-    cpu = None
-    if rank == 0 and not args.no_cpu and world == 1:
-        cpu = cpu_baseline_leg(ob, buf, pitch, n_per_stream, F, S, oraw, ncpu, args, nv)
-        cpu["reference_check"] = reference_check(ob, buf.download(n_per_stream * 4, dtype=np.int16).reshape(-1, 2), order) if raw else None
+        # ---- CPU baseline (rank 0, N = 1 leg of the contract; BASELINE.md 3: one thread AND all physical cores) -------
+        cpu = None
+        if rank == 0 and not args.no_cpu and world == 1:
+            cpu = cpu_baseline_leg(ob, buf, pitch, n_per_stream, F, S, oraw, ncpu, args, nv)
+            cpu["reference_check"] = reference_check(ob, buf.download(n_per_stream * 4, dtype=np.int16).reshape(-1, 2), order) if raw else None
     pipe.reset()
 
     # ---- warm-up, then EXACTLY K timed steps ------------------------------------
@@ -515,20 +548,21 @@ def main():
     if args.dump_outputs and rank == 0:
         dump_outputs(args.dump_outputs, nv, pipe, dump_ids, dump_before)
 
-    # ---- parity AFTER the timed region: what the measured launches produced.  The handle was reset before the warm-up;
-    # since then it has run the same F frames (warmup + steps) times, its filter and demodulator state carried from launch
-    # to launch (the reference's statics: receiver/fir1cpp.C:51-60, fir2cpp.C:74-83, fir3cpp.h:90-95, decoder.h:31-60) through
-    # ~(warmup + steps) x S x F unit hand-overs.  The oracle is fed the same frames as many times; every bit must agree.
-    loops = args.warmup + args.steps
-    ids_after = fullsize.spread(S, min(S, max(32, args.after_timed)))
-    checked_after, bad_after, after_s = fullsize.verify_replay(ob, buf, pitch, n_per_stream, oraw, lambda s: pipe.bits(s, 0), ids_after, ncpu, loops,
-                                                                   gpu_count=lambda s: pipe.bit_count(s, 0))
-    if bad_after:
-        print(f"PARITY FAILURE AFTER THE TIMED REGION (rank {rank}): {len(bad_after)} of {checked_after} streams differ from the CPU oracle "
-              f"after {loops} launches, first {bad_after[:8]}", file=sys.stderr)
-    parity_after = ranks.reduce(0.0 if bad_after else 1.0, "min") > 0.5
-    checked_after_all = int(ranks.reduce(float(checked_after), "sum"))
-    parity = parity and parity_after
+    if args.full:
+        # ---- parity AFTER the timed region: what the measured launches produced.  The handle was reset before the warm-up;
+        # since then it has run the same F frames (warmup + steps) times, its filter and demodulator state carried from launch
+        # to launch (the reference's statics: receiver/fir1cpp.C:51-60, fir2cpp.C:74-83, fir3cpp.h:90-95, decoder.h:31-60) through
+        # ~(warmup + steps) x S x F unit hand-overs.  The oracle is fed the same frames as many times; every bit must agree.
+        loops = args.warmup + args.steps
+        ids_after = fullsize.spread(S, min(S, max(32, args.after_timed)))
+        checked_after, bad_after, after_s = fullsize.verify_replay(ob, buf, pitch, n_per_stream, oraw, lambda s: pipe.bits(s, 0), ids_after, ncpu, loops,
+                                                                       gpu_count=lambda s: pipe.bit_count(s, 0))
+        if bad_after:
+            print(f"PARITY FAILURE AFTER THE TIMED REGION (rank {rank}): {len(bad_after)} of {checked_after} streams differ from the CPU oracle "
+                  f"after {loops} launches, first {bad_after[:8]}", file=sys.stderr)
+        parity_after = ranks.reduce(0.0 if bad_after else 1.0, "min") > 0.5
+        checked_after_all = int(ranks.reduce(float(checked_after), "sum"))
+        parity = parity and parity_after
     stale, seal_failures, _ = pipe.integrity_stats()
     stale_all = int(ranks.reduce(float(stale), "sum"))
     seal_failures_all = int(ranks.reduce(float(seal_failures), "sum"))
@@ -574,6 +608,18 @@ def main():
                    "chains_per_stream": 1,
                    "parallelism": f"streams sharded {world} ways, no collective"},
         "roofline": roofline,
+        "full": args.full,
+        "host_threads": place["threads"], "placement": place,
+        "ranks": ranks.describe(own_elapsed / args.steps * 1e3, checked, casc_avg, device),
+        "hbm_gbs_whole_job": round(world * bytes_per_step * args.steps / elapsed / 1e9, 1),
+        "gen_seconds": round(t_gen, 1), "bits_sampled": int(total_bits),
+    }
+    pipe.close()
+    if not args.full:
+        buf.free()
+        finish(line, parity, ranks, rank)
+        return
+    line.update({
         "cpu_baseline": cpu,
         "parity": parity, "parity_streams_checked": checked_all, "parity_seconds": round(verify_s, 1),
         "parity_after_timed": parity_after, "parity_after_timed_streams": checked_after_all, "parity_after_timed_launches": loops,
@@ -583,12 +629,7 @@ def main():
         "demod": {"near_ties": near_all, "min_relative_margin": margin_all, "timing_evaluations_rank0": int(evals),
                   "span_note": "roofline.demod_span_ms is first-to-last event of the demodulator of launch k, which runs BESIDE the "
                                "cascade of launch k+1 (second stream) and becomes resident as CUs have room: alone it takes ~0.85 ms"},
-        "host_threads": place["threads"], "placement": place,
-        "ranks": ranks.describe(own_elapsed / args.steps * 1e3, checked, casc_avg, device),
-        "hbm_gbs_whole_job": round(world * bytes_per_step * args.steps / elapsed / 1e9, 1),
-        "gen_seconds": round(t_gen, 1), "bits_sampled": int(total_bits),
-    }
-    pipe.close()
+    })
     legs_failed = []
 
     def run_leg(name, fn):

@@ -98,6 +98,23 @@ def test_a_leg_that_raises_fails_the_run_with_status_4(tmp_path, capsys):
     bench.finish(line, True, NoRanks(), 0, leg_errors=False)      # returns
 
 
+def test_options_of_full_are_refused_in_a_plain_run(monkeypatch, capsys):
+    """The options that shape what --full adds (checks, CPU baseline, side legs) end a plain run in the parser (status 2,
+    before any GPU call): a command that counted on a check cannot lose it quietly.  With --full they are taken."""
+    import bench
+    for opts in (["--no-cpu"], ["--verify", "32"], ["--no-legs", "--no-stage0-extra"], ["--after-timed", "128"], ["--cic3-verify", "8"],
+                 ["--cpu-streams", "4"], ["--allow-leg-errors"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"] + opts)
+        with pytest.raises(SystemExit) as e:
+            bench.parse()
+        err = capsys.readouterr().err.strip().splitlines()[-1]
+        assert e.value.code == 2 and "--full" in err and all(o in err for o in opts if o.startswith("--")), (opts, err)
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3", "--full"] + opts)
+        assert bench.parse().full
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", "d"])
+    assert not bench.parse().full
+
+
 def test_dump_outputs_is_a_fixed_sample_in_float_within_64_mb(tmp_path):
     """--dump-outputs: the same seeded sample of streams for the same arguments; every file float32/float64; the bits row of a
     stream is what it decoded after the warm-up (1 = 'B'), the most recent ones when a long run would overrun the 64 MB."""
@@ -162,9 +179,9 @@ def test_self_launch_passes_a_signal_on_to_its_ranks(tmp_path):
 # ------------------------------------------------------------------------------------------------ GPU
 @pytest.mark.gpu
 def test_bench_checks_the_timed_launches_and_reports_the_seals():
-    """The real bench.py at test size with every side leg: parity gated before AND after the timed region, in the headline
-    and in each leg; the seals' counters in the line (0 stale hand-overs); no leg failed; exit status 0."""
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--streams", "256", "--frames", "4", "--steps", "5", "--warmup", "2", "--cpu-streams", "8"],
+    """The real bench.py --full at test size with every side leg: parity gated before AND after the timed region, in the
+    headline and in each leg; the seals' counters in the line (0 stale hand-overs); no leg failed; exit status 0."""
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--streams", "256", "--frames", "4", "--steps", "5", "--warmup", "2", "--cpu-streams", "8"],
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = _line(out)
@@ -185,18 +202,23 @@ def test_bench_checks_the_timed_launches_and_reports_the_seals():
 
 @pytest.mark.gpu
 def test_bench_dump_outputs_are_the_last_timed_step_and_repeat_exactly(nv, oracle, tmp_path):
-    """bench.py --dump-outputs at test size, twice: the two dumps are identical, file for file; y3 is the last timed launch's
-    cascade output bit for bit and each bits row is what the stream decoded after the warm-up -- the oracle fed the stream's
-    frames warmup + steps times says so."""
+    """bench.py --dump-outputs at test size, twice -- with --full, then plain: the two dumps are identical, file for file,
+    so the plain run computes what the checked one does; y3 is the last timed launch's cascade output bit for bit and each
+    bits row is what the stream decoded after the warm-up -- the oracle fed the stream's frames warmup + steps times says so."""
     warmup, steps, S, F = 2, 3, 64, 4
     dumps = []
-    for run in range(2):
+    for run, extra in enumerate((["--full", "--no-cpu", "--no-legs", "--no-stage0-extra", "--after-timed", "32"], [])):
         d = tmp_path / f"run{run}"
         out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--streams", str(S), "--frames", str(F), "--steps", str(steps),
-                              "--warmup", str(warmup), "--no-cpu", "--no-legs", "--no-stage0-extra", "--after-timed", "32", "--dump-outputs", str(d)],
+                              "--warmup", str(warmup), "--dump-outputs", str(d)] + extra,
                              capture_output=True, text=True, timeout=900)
         assert out.returncode == 0, out.stderr[-3000:]
-        assert _line(out)["steps"] == steps and _line(out)["parity"] is True
+        rec = _line(out)
+        assert rec["steps"] == steps and rec["warmup"] == warmup and rec["full"] is bool(extra)
+        if extra:
+            assert rec["parity"] is True
+        else:
+            assert not {"parity", "cpu_baseline", "legs_failed"} & set(rec)
         dumps.append({f.stem: np.load(f) for f in d.glob("*.npy")})
     a, b = dumps
     assert set(a) == set(b) == {"y3", "bits", "bit_counts", "stream_ids"}
@@ -227,7 +249,7 @@ def test_bench_group_mode_two_members_on_one_gpu():
     multi-GPU box runs the same command without the override), same JSON line, parity before and after the timed region
     per member."""
     env = dict(os.environ, NVX_BENCH_GROUP_DEVICES="0,0")
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--group", "--streams", "96", "--frames", "6", "--steps", "3", "--warmup", "1"],
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--group", "--full", "--streams", "96", "--frames", "6", "--steps", "3", "--warmup", "1"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = _line(out)

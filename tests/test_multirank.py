@@ -139,7 +139,7 @@ def test_two_ranks_on_one_gpu_run_the_hip_path_and_check_their_own_shards(tmp_pa
     import json
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", NVX_BENCH_BACKEND="gloo", NVX_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(free_port()), str(ROOT / "bench.py"), "--gpus", "2", "--streams", "96", "--frames", "6",
+                          "--master-port", str(free_port()), str(ROOT / "bench.py"), "--gpus", "2", "--full", "--streams", "96", "--frames", "6",
                           "--steps", "2", "--warmup", "1", "--no-cpu"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -204,7 +204,7 @@ def test_plain_bench_gpus_2_runs_two_ranks_on_one_gpu():
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     env.update(NVX_BENCH_BACKEND="gloo", NVX_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--streams", "96", "--frames", "6", "--steps", "2", "--warmup", "1", "--no-cpu"],
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--full", "--streams", "96", "--frames", "6", "--steps", "2", "--warmup", "1", "--no-cpu"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     assert len(out.stdout.splitlines()) == 1
@@ -225,7 +225,7 @@ def test_rccl_calls_of_the_multi_gpu_run_on_one_gpu():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE")}
     env.update(NVX_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-                          "--master-port", str(free_port()), str(ROOT / "bench.py"), "--gpus", "1", "--streams", "96", "--frames", "6",
+                          "--master-port", str(free_port()), str(ROOT / "bench.py"), "--gpus", "1", "--full", "--streams", "96", "--frames", "6",
                           "--steps", "2", "--warmup", "1", "--no-cpu", "--no-legs", "--no-stage0-extra", "--verify", "32"],
                          env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -5,7 +5,7 @@ V=$1; VALS=$2; shift 2
 mkdir -p $R/gpurun_out; L=$R/gpurun_out/env_sweep.log; : > $L
 for round in $(seq 1 ${ROUNDS:-2}); do for val in $VALS; do
     echo "== $V=$val" >> $L
-    env $V=$val timeout -k 10 300 python bench.py --no-cpu --no-stage0-extra --no-legs --verify 32 "$@" 2>/dev/null >> $L || { echo FAILED >> $L; tail -5 $L; exit 1; }
+    env $V=$val timeout -k 10 300 python bench.py --full --no-cpu --no-stage0-extra --no-legs --verify 32 "$@" 2>/dev/null >> $L || { echo FAILED >> $L; tail -5 $L; exit 1; }
 done; done
 python - <<PY
 import json, collections, statistics

@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
 O=$R/gpurun_out/gaps; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/t -- python3 bench.py --no-cpu --no-legs --no-stage0-extra --verify 32 --steps 10 --warmup 3 > $O/trace.log 2>&1; echo "trace rc=$?"
+timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/t -- python3 bench.py --full --no-cpu --no-legs --no-stage0-extra --verify 32 --steps 10 --warmup 3 > $O/trace.log 2>&1; echo "trace rc=$?"
 grep -h '^{' $O/trace.log | tail -1 | cut -c1-300
 f=$(find $O -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'

@@ -7,10 +7,10 @@ cd $R
 for round in $(seq 1 ${ROUNDS:-3}); do for lib in "$@"; do
     if [ "$lib" = "-" ]; then unset NAVTEX_AMD_LIB; else export NAVTEX_AMD_LIB=$R/$lib; fi
     echo "== $lib variant_a" >> $L
-    timeout -k 10 300 python3 bench.py --variant-a --frames 96 --steps 5 --warmup 1 --no-cpu --verify 16 2>/dev/null >> $L; rc=$?
+    timeout -k 10 300 python3 bench.py --full --variant-a --frames 96 --steps 5 --warmup 1 --no-cpu --verify 16 2>/dev/null >> $L; rc=$?
     [ $rc -ne 0 ] && [ $rc -ne 3 ] && { echo "FAILED rc=$rc" >> $L; tail -5 $L; exit 1; }
     echo "== $lib wideband" >> $L
-    timeout -k 10 200 python3 bench.py --wideband 512 --frames 12 --steps 10 --warmup 2 --no-cpu --verify 16 2>/dev/null >> $L; rc=$?
+    timeout -k 10 200 python3 bench.py --full --wideband 512 --frames 12 --steps 10 --warmup 2 --no-cpu --verify 16 2>/dev/null >> $L; rc=$?
     [ $rc -ne 0 ] && [ $rc -ne 3 ] && { echo "FAILED rc=$rc" >> $L; tail -5 $L; exit 1; }
 done; done
 python3 - <<PY

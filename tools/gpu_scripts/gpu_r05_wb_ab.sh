@@ -8,7 +8,7 @@ cd $R
 for round in $(seq 1 ${ROUNDS:-4}); do for lib in "$@"; do
     if [ "$lib" = "-" ]; then unset NAVTEX_AMD_LIB; else export NAVTEX_AMD_LIB=$R/$lib; fi
     echo "== $lib" >> $L
-    timeout -k 10 200 python3 bench.py --wideband 512 --frames 12 --steps 10 --warmup 2 --no-cpu --verify 16 2>/dev/null >> $L; rc=$?
+    timeout -k 10 200 python3 bench.py --full --wideband 512 --frames 12 --steps 10 --warmup 2 --no-cpu --verify 16 2>/dev/null >> $L; rc=$?
     [ $rc -ne 0 ] && [ $rc -ne 3 ] && { echo "FAILED rc=$rc" >> $L; tail -5 $L; exit 1; }
 done; done
 python3 - <<PY

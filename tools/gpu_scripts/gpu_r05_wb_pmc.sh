@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
 O=$R/gpurun_out/r05wbpmc; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-B="python3 bench.py --no-cpu --no-legs --verify 16 --steps 4 --warmup 1 --wideband 512 --frames 12"
+B="python3 bench.py --full --no-cpu --no-legs --verify 16 --steps 4 --warmup 1 --wideband 512 --frames 12"
 P1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU"
 P2="SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_INSTS_SALU SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE SQ_INSTS_LDS"
 for spec in "$@"; do
@@ -17,7 +17,7 @@ done
 python3 - $O "$@" > $O/pmc.txt <<'PY'
 import csv, glob, sys, collections
 O = sys.argv[1]
-print("rocprofv3 --pmc, two separate passes per build; bench.py --no-cpu --no-legs --verify 16 --steps 4 --warmup 1 --wideband 512 --frames 12; per kernel: LAST dispatch; SQ_* cycle counters are quad-cycles")
+print("rocprofv3 --pmc, two separate passes per build; bench.py --full --no-cpu --no-legs --verify 16 --steps 4 --warmup 1 --wideband 512 --frames 12; per kernel: LAST dispatch; SQ_* cycle counters are quad-cycles")
 for spec in sys.argv[2:]:
     tag = spec.split("=")[0]
     for p in ("1", "2"):

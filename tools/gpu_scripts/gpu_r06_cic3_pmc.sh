@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
 O=$R/gpurun_out/r06cic3; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-B="python3 bench.py --no-cpu --no-stage0-extra --no-legs --verify 32 --steps 4 --warmup 1"
+B="python3 bench.py --full --no-cpu --no-stage0-extra --no-legs --verify 32 --steps 4 --warmup 1"
 pmc() { local d=$1; shift; local ctr=(); while [ "$1" != "--" ]; do ctr+=("$1"); shift; done; shift
     timeout -k 10 280 rocprofv3 --pmc "${ctr[@]}" --output-format csv -d $O/$d -- $B "$@" > $O/$d.log 2>&1; echo "$d rc=$?"; }
 P1="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU"

@@ -6,11 +6,11 @@ R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
 O=$R/gpurun_out/r06final; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/trace.log 2>&1; echo "trace rc=$?"
+timeout -k 10 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/trace.log 2>&1; echo "trace rc=$?"
 grep -h '^{' $O/trace.log | tail -1 > $O/bench_under_rocprof.json
 cat $O/trace/*/*kernel_stats.csv > $O/kernel_stats.csv
-B="python3 bench.py --no-cpu --no-stage0-extra --no-legs --verify 32 --steps 4 --warmup 1"
+B="python3 bench.py --full --no-cpu --no-stage0-extra --no-legs --verify 32 --steps 4 --warmup 1"
 pmc() {  # dir, counters..., then -- bench args
     local d=$1; shift; local ctr=(); while [ "$1" != "--" ]; do ctr+=("$1"); shift; done; shift
     timeout -k 10 280 rocprofv3 --pmc "${ctr[@]}" --output-format csv -d $O/$d -- $B "$@" > $O/$d.log 2>&1; echo "$d rc=$?"
@@ -26,7 +26,7 @@ O = sys.argv[1]
 import importlib.util
 spec = importlib.util.spec_from_file_location("bench_for_hash", "bench.py"); b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
 print("# kernel sources", b.kernel_source_hash(), "(bench.py: KERNEL_SOURCES)")
-print("rocprofv3 --pmc, separate passes; bench.py --no-cpu --no-stage0-extra --no-legs --verify 32 --steps 4 --warmup 1 [+ --stage0 cic3 | --wideband 512 --frames 12]; per kernel: LAST dispatch; SQ_* cycle counters are quad-cycles")
+print("rocprofv3 --pmc, separate passes; bench.py --full --no-cpu --no-stage0-extra --no-legs --verify 32 --steps 4 --warmup 1 [+ --stage0 cic3 | --wideband 512 --frames 12]; per kernel: LAST dispatch; SQ_* cycle counters are quad-cycles")
 for p in ("h1", "h2", "h3", "h4", "c3", "c4", "w1", "w2", "w3", "w4"):
     for f in glob.glob(f"{O}/{p}/**/*counter_collection.csv", recursive=True):
         rows = list(csv.DictReader(open(f)))

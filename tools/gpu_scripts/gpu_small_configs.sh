@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
 O=$R/gpurun_out/small; rm -rf $O; mkdir -p $O
 cd $R
 for S in 1 3 16 64; do
-    timeout -k 10 300 python3 bench.py --streams $S --frames 62 --steps 200 --warmup 10 --no-cpu --no-legs --no-stage0-extra > $O/s$S.json 2> $O/s$S.err || { echo "S=$S failed"; tail -3 $O/s$S.err; exit 1; }
+    timeout -k 10 300 python3 bench.py --full --streams $S --frames 62 --steps 200 --warmup 10 --no-cpu --no-legs --no-stage0-extra > $O/s$S.json 2> $O/s$S.err || { echo "S=$S failed"; tail -3 $O/s$S.err; exit 1; }
     python3 - $O/s$S.json $S <<'PY'
 import json, sys
 j = json.load(open(sys.argv[1]))

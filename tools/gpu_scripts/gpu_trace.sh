@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
 O=$R/gpurun_out/trace; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/t -- python3 bench.py --no-cpu --steps 6 --warmup 2 > $O/trace.log 2>&1; echo "trace rc=$?"
+timeout -k 10 400 rocprofv3 --kernel-trace --output-format csv -d $O/t -- python3 bench.py --full --no-cpu --steps 6 --warmup 2 > $O/trace.log 2>&1; echo "trace rc=$?"
 f=$(find $O -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys

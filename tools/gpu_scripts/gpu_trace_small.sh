@@ -5,7 +5,7 @@ cd $R
 export TMPDIR=/tmp
 S=${1:-1}; F=${2:-62}
 O=gpurun_out/trace_small; rm -rf $O; mkdir -p $O
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O -- python3 bench.py --streams $S --frames $F --steps 12 --warmup 3 --no-cpu --no-legs --no-stage0-extra --verify 1 > $O/log.txt 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O -- python3 bench.py --full --streams $S --frames $F --steps 12 --warmup 3 --no-cpu --no-legs --no-stage0-extra --verify 1 > $O/log.txt 2>&1
 python3 - <<'PY'
 import csv, glob
 f = glob.glob("gpurun_out/trace_small/**/*kernel_trace.csv", recursive=True)[0]
