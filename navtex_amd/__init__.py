@@ -187,6 +187,19 @@ class HandleStats:
         N.check(lib.nvx_signal_report_read(self._h, stream, chain, C.byref(r), int(reset)), "nvx_signal_report_read")
         return {f: getattr(r, f) for f, _ in N.SignalReport._fields_}
 
+    def set_carrier(self, stream: int, chain: int, offset_hz: float) -> float:
+        """Tune (stream, chain) to offset_hz from its stream's centre (nvx_set_carrier, include/navtex_amd_tune.h): from the
+        stream's next launch on; returns the offset applied (a multiple of 3.125 Hz)."""
+        applied = C.c_double()
+        N.check(lib.nvx_set_carrier(self._h, stream, chain, float(offset_hz), C.byref(applied)), "nvx_set_carrier")
+        return applied.value
+
+    def carrier(self, stream: int, chain: int) -> Tuple[float, bool]:
+        """(offset in Hz, runs the reference mixer) of (stream, chain) -- nvx_get_carrier."""
+        off, ref = C.c_double(), C.c_int()
+        N.check(lib.nvx_get_carrier(self._h, stream, chain, C.byref(off), C.byref(ref)), "nvx_get_carrier")
+        return off.value, bool(ref.value)
+
 
 
 class Pipeline(HandleStats):
@@ -462,6 +475,18 @@ class Group:
         if m < 0:
             raise ValueError(f"stream {stream} is not in the group")
         return self.member_view(m).signal_report(stream - self.members[m][1], chain, reset)
+
+    def set_carrier(self, stream: int, chain: int, offset_hz: float) -> float:
+        """Tune global stream `stream`'s chain (nvx_group_set_carrier: the member that owns it); returns the offset applied."""
+        applied = C.c_double()
+        N.check(lib.nvx_group_set_carrier(self._g, stream, chain, float(offset_hz), C.byref(applied)), "nvx_group_set_carrier")
+        return applied.value
+
+    def carrier(self, stream: int, chain: int) -> Tuple[float, bool]:
+        """(offset in Hz, runs the reference mixer) of global stream `stream`'s chain -- nvx_group_get_carrier."""
+        off, ref = C.c_double(), C.c_int()
+        N.check(lib.nvx_group_get_carrier(self._g, stream, chain, C.byref(off), C.byref(ref)), "nvx_group_get_carrier")
+        return off.value, bool(ref.value)
 
     def process_resident(self, ptrs: Sequence[int], pitch: int, first_frame: int, n_frames: int) -> None:
         arr = (C.c_void_p * len(ptrs))(*ptrs)

@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cmath>
 #include "navtex_amd_signal.h"
+#include "navtex_amd_tune.h"
 #include "nvx_fsm.h"
 
 // ------------------------------------------------------------------ errors
@@ -213,7 +214,12 @@ extern "C" int nvx_create(const nvx_config *cfg, nvx_handle **out)
     CR_MAKE(event, h->launch_done, hipEventCreateWithFlags(&h->launch_done, hipEventDisableTiming));
     std::vector<uint8_t> active(h->n_slots);
     for (int i = 0; i < h->n_slots; i++) active[i] = h->slots[i].active;
-    CR_MAKE(device, h->d_masks, hipMalloc(&h->d_masks, h->n_streams));
+    // the chain masks, then every chain's carrier k (navtex_amd_tune.h; nvx_kernels.h, NVX_TUNE_K_OFFSET): at its nominal k
+    h->tune_k.resize(h->n_slots);
+    for (int i = 0; i < h->n_slots; i++) h->tune_k[i] = (i & 1) ? -NVX_TUNE_NOMINAL_K : NVX_TUNE_NOMINAL_K;
+    CR_MAKE(device, h->d_masks, hipMalloc(&h->d_masks, NVX_TUNE_K_OFFSET(h->n_streams) + (size_t)h->n_slots * sizeof(int)));
+    h->d_tune_k = (int *)(h->d_masks + NVX_TUNE_K_OFFSET(h->n_streams));
+    CR_TRY(hipMemcpy(h->d_tune_k, h->tune_k.data(), (size_t)h->n_slots * sizeof(int), hipMemcpyHostToDevice));
     CR_MAKE(device, h->d_active, hipMalloc(&h->d_active, h->n_slots));
     CR_TRY(hipMemcpy(h->d_masks, h->masks.data(), h->n_streams, hipMemcpyHostToDevice));
     CR_TRY(hipMemcpy(h->d_active, active.data(), h->n_slots, hipMemcpyHostToDevice));
@@ -458,6 +464,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
         ca.queue = h->d_ctrl; ca.status = h->d_ctrl + 1; ca.done = h->d_ctrl + NVX_CASCADE_CTRL_INTS;
         ca.stage0_order = h->cfg.stage0_order;
         ca.third0 = third0;
+        ca.tune_k = h->d_tune_k;
         ca.max_waves_per_cu = -1;                        // one fewer than fit: room for the previous launch's demodulator (above)
         HIP_TRY(nvx_launch_cascade(&ca, h->cascade_raw, h->nch, st));
     }
@@ -833,6 +840,39 @@ extern "C" int nvx_enable_signal_report(nvx_handle *h, int on)
     }
     h->sig_stride = stride;
     h->sig_on = true;
+    return NVX_OK;
+}
+
+// Carrier tuning (navtex_amd_tune.h).  The launches in flight keep the k they were launched with: the handle's work is
+// waited for, then the device array is rewritten, so the stream's next launch is the first with the new k.
+extern "C" int nvx_set_carrier(nvx_handle *h, int stream, int chain, double offset_hz, double *applied_hz)
+{
+    if (!h) { nvx_set_error("nvx_set_carrier: null handle"); return NVX_ERR_ARG; }
+    if (h->cfg.wideband) { nvx_set_error("nvx_set_carrier: not for wideband handles (the channeliser fixes their sub-bands)"); return NVX_ERR_STATE; }
+    if (stream < 0 || stream >= h->n_streams || chain < 0 || chain > 1) { nvx_set_error("nvx_set_carrier: bad stream or chain"); return NVX_ERR_ARG; }
+    if (!((h->masks[stream] >> chain) & 1)) { nvx_set_error("nvx_set_carrier: chain %d is not in stream %d's mask", chain, stream); return NVX_ERR_ARG; }
+    if (!std::isfinite(offset_hz) || std::fabs(offset_hz) > NVX_TUNE_MAX_HZ) { nvx_set_error("nvx_set_carrier: offset %g Hz outside +-%g Hz", offset_hz, NVX_TUNE_MAX_HZ); return NVX_ERR_ARG; }
+    const int k = (int)std::rint(offset_hz / NVX_TUNE_STEP_HZ);
+    std::lock_guard<std::mutex> lk(h->mu);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
+    const int slot = 2 * stream + chain;
+    HIP_TRY(hipMemcpyAsync(h->d_tune_k + slot, &k, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->tune_k[slot] = k;
+    if (applied_hz) *applied_hz = k * NVX_TUNE_STEP_HZ;
+    return NVX_OK;
+}
+
+extern "C" int nvx_get_carrier(nvx_handle *h, int stream, int chain, double *offset_hz, int *reference_mixer)
+{
+    if (!h) { nvx_set_error("nvx_get_carrier: null handle"); return NVX_ERR_ARG; }
+    if (h->cfg.wideband) { nvx_set_error("nvx_get_carrier: not for wideband handles"); return NVX_ERR_STATE; }
+    if (stream < 0 || stream >= h->n_streams || chain < 0 || chain > 1) { nvx_set_error("nvx_get_carrier: bad stream or chain"); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    const int k = h->tune_k[2 * stream + chain];
+    if (offset_hz) *offset_hz = k * NVX_TUNE_STEP_HZ;
+    if (reference_mixer) *reference_mixer = k == (chain ? -NVX_TUNE_NOMINAL_K : NVX_TUNE_NOMINAL_K);
     return NVX_OK;
 }
 

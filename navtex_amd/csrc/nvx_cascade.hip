@@ -4,7 +4,7 @@
 //   nvx_fir_cascade<RAW, NCH>            int16 IQ in HBM -> 900 S/s complex fp64 per chain
 //        stage 0 (/8 integer, build-owned, RAW only)
 //        FIR1 37 taps /4        receiver/fir1cpp.C:80-136
-//        mixer +-14 kHz         receiver/fir2cpp.C:112-128
+//        mixer +-14 kHz         receiver/fir2cpp.C:112-128 (or a tuned carrier: navtex_amd_tune.h)
 //        FIR2 47 taps /7        receiver/fir2cpp.C:131-215
 //        FIR3 71 taps /10       receiver/fir3cpp.C:22-60
 //   nvx_demod_front + nvx_demod_fsm      900 S/s -> 'B'/'Y' bits
@@ -60,6 +60,11 @@
 #include <mutex>
 
 #include "nvx_cascade_wave.h"
+#include "nvx_tune_table.h"
+
+// The mixer's table (nvx_kernels.h, NVX_TUNE_TAB_ENTRIES): the same on every device and for every handle, written by the
+// launcher before the first launch on a device (tune_table_ready below)
+__device__ double2 nvx_tune_tab[NVX_TUNE_TAB_ENTRIES];
 
 // stage 0 for one 1-KiB load: lane l holds raw samples 4l..4l+3 of the KiB;
 // lanes (2i, 2i+1) together hold the 8 samples of output i.  Even lanes produce
@@ -349,8 +354,9 @@ __device__ __forceinline__ void cascade_wave_main(ARGS a)
         const u32x4 *src = unit0 - (size_t)pre * pass_stride;
         if (preroll) load_pass<RAW>(pfA, src);
         const u32x4 *nxt = src + pass_stride;          // first pass not yet requested (one pass of prefetch; two measured null)
-        // mixer index of the unit's first FIR1 output: 6720 * third mod 9 (0 at every frame start; the pre-roll starts
-        // 576 = 0 mod 9 outputs earlier: same index); FIR3 outputs of the pre-roll are not written
+        // reference mixer index of the unit's first FIR1 output (the fused wideband kernel's LDS table; this kernel's mixer
+        // reads the table below): 6720 * third mod 9 (0 at every frame start; the pre-roll starts 576 = 0 mod 9 outputs
+        // earlier: same index); FIR3 outputs of the pre-roll are not written
         cw.begin_unit(mask, a.y3, (size_t)(stream * 2) * a.y3_cap + a.y3_base + (size_t)part * NVX_THIRD_Y3, a.y3_cap,
                       ((part % 3) * (NVX_THIRD_PASSES * 64)) % NVX_MIX_N,
                       preroll ? NVX_PREROLL_U : 0, preroll ? NVX_PREROLL_Y2 : 0, !preroll);
@@ -358,8 +364,19 @@ __device__ __forceinline__ void cascade_wave_main(ARGS a)
         if (preroll) cw.state_zero();
         NVX_WAVE_LDS_FENCE();
         if (S0 == 3) { s0.c_prev = (int)(unsigned)ct; s0.t_prev = (int)(unsigned)(ct >> 32); }
+        // Carrier tuning (navtex_amd_tune.h): the stream's two k in one scalar load; the mixer of every unit takes its
+        // coefficients from nvx_tune_tab (nvx_kernels.h, CascadeWave::begin_table_mix).  The unit's first FIR1
+        // output within its frame: (part mod 3) thirds of 6720, a pre-roll 576 earlier.
+        {
+            const unsigned long long k01 = nvx_load_const_u64(a.tune_k + 2 * stream);
+            int o_first = (part % 3) * (NVX_THIRD_PASSES * 64) - pre * 64;
+            if (o_first < 0) o_first += NVX_PASSES_PER_FRAME * 64;
+            cw.begin_table_mix((int)(unsigned)k01, (int)(unsigned)(k01 >> 32), o_first);
+        }
 
         auto body = [&](u32x4 (&pf)[NPF], const int pass) {
+            // ---- the mixer's coefficients: requested in front of stage 0, whose work covers their L2 latency
+            cw.tune_fetch(nvx_tune_tab);
             // ---- 1. new 252 kS/s samples into the polyphase window ----------
             if (RAW) {
 #pragma unroll
@@ -374,12 +391,15 @@ __device__ __forceinline__ void cascade_wave_main(ARGS a)
                     xw4[r * XS] = v;
                 }
             }
+            // ---- ... and waited for here, ahead of the prefetch: waited for behind it (at the mixer), they would make the
+            // wave wait for the prefetch too (a conditional load: the compiler can only count it as vmcnt(0))
+            cw.tune_ready();
             // ---- 2. prefetch the next pass into the buffer just consumed --------------
             if (pass + 1 < n_pass) load_pass<RAW>(pf, nxt);
             nxt += pass_stride;
             NVX_WAVE_LDS_FENCE();
             // ---- 3.-7. FIR1, mixer, history slide, FIR2 / FIR3 when their batches are full
-            cw.compute_pass();
+            cw.compute_pass(true);
         };
 
         for (int pass = 0; pass < n_pass; pass++) {
@@ -511,8 +531,35 @@ static hipError_t launch_cascade_as(const nvx_cascade_args *a, hipStream_t s)
     return hipGetLastError();
 }
 
+// nvx_tune_tab of the current device: T from the generated octant (nvx_tune_entry), and the reference's entries where a
+// nominal k reaches them.  Once per device and process; the copy is synchronous, in front of the first launch.
+static hipError_t tune_table_ready()
+{
+    static std::mutex mu;
+    static bool done[NVX_MAX_DEVICES];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= NVX_MAX_DEVICES) return hipErrorInvalidDevice;
+    std::lock_guard<std::mutex> lk(mu);
+    if (done[dev]) return hipSuccess;
+    double2 *tab = (double2 *)calloc(NVX_TUNE_TAB_ENTRIES, sizeof(double2));
+    if (!tab) return hipErrorOutOfMemory;
+    for (int j = 0; j < NVX_TUNE_TAB_N; j++) nvx_tune_entry(j, &tab[j].x, &tab[j].y);
+    for (int o = 0; o < NVX_MIX_N; o++) {
+        const int j = (NVX_TUNE_NOMINAL_K * o) % NVX_TUNE_TAB_N;
+        tab[NVX_TUNE_TAB_N + j] = double2{ NVX_MIX_CR[o], NVX_MIX_CI[o] };
+        tab[2 * NVX_TUNE_TAB_N + (NVX_TUNE_TAB_N - j) % NVX_TUNE_TAB_N] = double2{ NVX_MIX_CR[o], -NVX_MIX_CI[o] };
+    }
+    e = hipMemcpyToSymbol(HIP_SYMBOL(nvx_tune_tab), tab, NVX_TUNE_TAB_ENTRIES * sizeof(double2), 0, hipMemcpyHostToDevice);
+    free(tab);
+    if (e == hipSuccess) done[dev] = true;
+    return e;
+}
+
 extern "C" hipError_t nvx_launch_cascade(const nvx_cascade_args *a, int raw, int nch, hipStream_t s)
 {
+    { hipError_t e = tune_table_ready(); if (e != hipSuccess) return e; }
     // queue counter, status word and per-stream completion counts start at zero every launch
     hipError_t e = hipMemsetAsync(a->queue, 0, (size_t)(NVX_CASCADE_CTRL_INTS + a->n_streams) * sizeof(int), s);
     if (e != hipSuccess) return e;

@@ -215,6 +215,11 @@ struct CascadeWave {
     // !F3IN: where this lane's FIR2 outputs go -- the unit's first output of the lane's chain in the y2 buffer (nullptr: the
     // chain is not decoded) -- and how many outputs per chain the unit has written so far
     double2 *y2_lane; int n2_done;
+    // the mixer of the single-wave cascade kernels (navtex_amd_tune.h), per chain slot: where its coefficients start in
+    // the table and k mod N (wave-uniform); per lane the table index of its output in the next pass (output 2 half + comp:
+    // the lane pair splits the pair's two coefficients), and this pass's coefficient
+    int toff[NCH], tk[NCH], tidx[NCH];
+    nvx_d2 tc[NCH];
 
     // once per kernel: lane constants, the taps, the mixer table of this wave's LDS block
     __device__ __forceinline__ void init(CascadeLds<NCH, F3IN> *l, int lane_)
@@ -222,7 +227,7 @@ struct CascadeWave {
         lds = l; lane = lane_; half = lane >> 1; comp = lane & 1;
         xrv = (const lds_vdouble *)((const double *)&lds->X[XH + half] + comp);
         lane_mod9 = (2 * half) % 9;
-        if (lane < 4 * NVX_MIX_N) {
+        if (!F3IN && lane < 4 * NVX_MIX_N) {
             // constant-index selects keep the tables out of scratch
             const int j9 = lane % NVX_MIX_N;
             double cr = 0.0, ci = 0.0;
@@ -251,7 +256,47 @@ struct CascadeWave {
         mixrow = (const lds_vd2 *)&lds->mix[(comp ^ (NCH == 1 ? chain_of_slot0 : 0)) ? 0 : 1][lane_mod9];
         y3 = y3_; y3_row0 = row0; y3_cap = cap;
         mixbase = mixbase0; n_u = n_u0; n_y2 = n_y20; n3_done = 0; n2_done = 0; emit = emit0;
-        mix_next = mixrow[mixbase];      // (behind init()'s table writes in this wave's LDS queue)
+        if (!F3IN) mix_next = mixrow[mixbase];      // (behind init()'s table writes in this wave's LDS queue)
+    }
+
+    // The table mixer (the single-wave cascade kernels), once per unit behind begin_unit: k of the stream's two chains,
+    // the FIR1 output index o_first in [0, N) of the unit's first pass (pre-roll included).  Chain slot c mixes output o
+    // with tab[toff + (k o) mod N]: a tuned chain reads T (toff 0); a chain at its nominal k reads the reference mixer's
+    // nine entries, placed where its k o mod N lands (multiples of 2240) in a table of its own (toff N: chain 0, 2N:
+    // chain 1, in the 518 form), so that it stays bit-identical to the reference (nvx_kernels.h, NVX_TUNE_TAB_ENTRIES).
+    __device__ __forceinline__ void begin_table_mix(int k0, int k1, int o_first)
+    {
+        int o = o_first + lane;                           // the lane's output of the first pass, 2 half + comp, mod N
+        if (o >= NVX_TUNE_TAB_N) o -= NVX_TUNE_TAB_N;
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            // (the chain mask arrives in a VGPR: readfirstlane keeps the chain's constants in scalar registers)
+            const int ch = __builtin_amdgcn_readfirstlane((NCH == 1) ? chain_of_slot0 : c);
+            const int k = ch ? k1 : k0;
+            const bool nominal = k == (ch ? -NVX_TUNE_NOMINAL_K : NVX_TUNE_NOMINAL_K);
+            tk[c] = ((k % NVX_TUNE_TAB_N) + NVX_TUNE_TAB_N) % NVX_TUNE_TAB_N;
+            toff[c] = nominal ? NVX_TUNE_TAB_N * (1 + ch) : 0;
+            tidx[c] = (tk[c] * o) % NVX_TUNE_TAB_N;          // k, o < N: the product stays below 2^31
+        }
+    }
+    // ... once per pass (nvx_cascade.hip: in front of stage 0): the coefficient of the lane's output
+    // 2 half + comp as one 16-byte load from the L2-resident table (the mixer swaps the pair's two: one load and four
+    // VGPRs per lane and chain, not two and eight); then the index moves on by 64 outputs
+    __device__ __forceinline__ void tune_fetch(const double2 *tab)
+    {
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            tc[c] = *(const nvx_d2 *)(tab + toff[c] + tidx[c]);
+            tidx[c] += (64 * tk[c]) % NVX_TUNE_TAB_N;
+            if (tidx[c] >= NVX_TUNE_TAB_N) tidx[c] -= NVX_TUNE_TAB_N;
+        }
+    }
+
+    // ... and the point where they must have arrived (the compiler waits for the load here, not at the mixer)
+    __device__ __forceinline__ void tune_ready()
+    {
+#pragma unroll
+        for (int c = 0; c < NCH; c++) asm volatile("" :: "v"(tc[c].x), "v"(tc[c].y));
     }
 
     // !F3IN, once per unit: the y2 buffer of the stream's parity, the rows of its two chains (-1: not decoded), the unit's
@@ -325,7 +370,9 @@ struct CascadeWave {
     }
 
     // One pass: the window holds 256 new samples (entries XH .. XH+31 of every phase) behind its history.
-    __device__ __forceinline__ void compute_pass()
+    // table_mix (the single-wave cascade kernels): the mixer takes this pass's coefficients from tune_fetch() instead of
+    // the reference's LDS table (the fused wideband kernel's mixer)
+    __device__ __forceinline__ void compute_pass(const bool table_mix = false)
     {
         // ---- FIR1: y1[o] = sum_i h1[i] * x[4o+3-i], outputs o = 2*half and 2*half+1 of component comp.
         // With s_j = x[8*half + 7 - j]:  y1[2*half+1] = sum_j h1[j] * s_j (j = 0..36),
@@ -337,8 +384,8 @@ struct CascadeWave {
         // the tail of the new samples that becomes the next pass's history -- so that neither costs a round trip
         // through the LDS with the wave idle.
         // (the lane's two outputs use table entries m and m + 1, the next pass's m + 1 and m + 2: one new entry per pass)
-        const nvx_d2 c0 = mix_next, c1 = mixrow[mixbase + 1];
-        mix_next = c1;
+        nvx_d2 c0 = { 0.0, 0.0 }, c1 = { 0.0, 0.0 };
+        if (!table_mix) { c0 = mix_next; c1 = mixrow[mixbase + 1]; mix_next = c1; }
         nvx_d2 tail = { 0.0, 0.0 };
         if (lane < XPH * XH) tail = *(const lds_vd2 *)&lds->X[(lane & 7) * XS + 32 + (lane >> 3)];
         double xs[NVX_T1 + 4];
@@ -369,7 +416,20 @@ struct CascadeWave {
         // A lane owns one component of its two outputs and gets the other from its partner lane (DPP pair swap).
         // With A = mine*cr and B = other*ci, both chains' results are A + B or A - B (a sum commutes exactly and
         // (-I)*ci = -(I*ci) exactly): 518 -> I lane A - B, Q lane A + B; 490 -> I lane A + B, Q lane A - B.
-        {
+        if (table_mix) {
+            // every chain slot its own coefficients (cr, ci), the 518 form: I lane A - B, Q lane A + B
+            const double o0 = dpp_swap_pairs_f64(a0), o1 = dpp_swap_pairs_f64(a1);
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                const nvx_d2 tp = { dpp_swap_pairs_f64(tc[c].x), dpp_swap_pairs_f64(tc[c].y) };   // the partner's coefficient
+                const nvx_d2 c0t = comp ? tp : tc[c], c1t = comp ? tc[c] : tp;                  // outputs 2 half, 2 half + 1
+                const double A0 = a0 * c0t.x, A1 = a1 * c1t.x;
+                const double B0 = o0 * c0t.y, B1 = o1 * c1t.y;
+                double *uw = (double *)&lds->U[c][46 + n_u + 2 * half] + comp;
+                uw[0] = comp ? A0 + B0 : A0 - B0;
+                uw[2] = comp ? A1 + B1 : A1 - B1;
+            }
+        } else {
             const double o0 = dpp_swap_pairs_f64(a0), o1 = dpp_swap_pairs_f64(a1);
             const double A0 = a0 * c0.x, A1 = a1 * c1.x;
             // the lane's table row holds +-ci: B carries the sign of the 518 chain (of the unit's only chain when
@@ -384,7 +444,7 @@ struct CascadeWave {
             }
         }
         n_u += 64;
-        mixbase += 1; if (mixbase == NVX_MIX_N) mixbase = 0;      // 64 mod 9 == 1
+        if (!table_mix) { mixbase += 1; if (mixbase == NVX_MIX_N) mixbase = 0; }     // 64 mod 9 == 1
         // ---- the 5-deep history of each phase moves to the front
         NVX_WAVE_LDS_FENCE();
         if (lane < XPH * XH) *(lds_vd2 *)&lds->X[(lane & 7) * XS + (lane >> 3)] = tail;

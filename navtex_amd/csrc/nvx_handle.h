@@ -158,6 +158,9 @@ struct nvx_handle {
     bool sig_on = false;
     nvx_sig_rec *d_sig_part = nullptr;
     int sig_stride = 0;
+    // carrier tuning (navtex_amd_tune.h): k per slot, and its device copy behind the chain masks (NVX_TUNE_K_OFFSET)
+    std::vector<int> tune_k;
+    int *d_tune_k = nullptr;
     int *d_di = nullptr;
     uint32_t *d_fsm_tab = nullptr;     // bit-period transition table of the demodulator FSM (nvx_fsm.h)
     unsigned short *d_words = nullptr;

@@ -113,7 +113,18 @@ typedef struct {
     int split_from;            /* set by the launcher: frames from this one on are handed out in thirds (n_frames = none) */
     unsigned third0;           /* position of the launch in its streams, in thirds of a frame since reset (g0 / 96), for the    */
                                /* state block's tag; with a list every entry carries its own g0                                */
+    const int *tune_k;         /* carrier tuning (navtex_amd_tune.h): [all streams][2] carrier k per chain, read with one scalar */
+                               /* load per unit (the host keeps it behind the chain masks, NVX_TUNE_K_OFFSET)                */
 } nvx_cascade_args;
+#define NVX_TUNE_NOMINAL_K 4480           /* chain 0; chain 1's is -4480 (+-14 kHz / 3.125 Hz) */
+#define NVX_TUNE_TAB_N 20160              /* = NVX_TUNE_N: FIR1 outputs per frame */
+/* The mixer's table of the cascade kernels (nvx_cascade.hip, nvx_tune_tab: device memory of the code object, uploaded by
+ * the launcher once per device): T (N entries), then for chain 0 and chain 1 a table of N entries of which the nine at
+ * k o mod N (k = +-4480: multiples of 2240) hold the reference mixer's entry of o in the 518 form (cos, +-sin) -- the
+ * mixer of a chain at its nominal k */
+#define NVX_TUNE_TAB_ENTRIES (3 * NVX_TUNE_TAB_N)
+/* the k array's place in the chain-mask allocation (bytes), n_streams masks in front */
+#define NVX_TUNE_K_OFFSET(n_streams) ((((size_t)(n_streams)) + 7) / 8 * 8)
 
 /* FIR3 as a kernel of its own (wideband handles, fused form): y2 rows -> y3, and the rows' tails into the other
  * buffer's prefix */
