@@ -1,6 +1,6 @@
-"""Build helper: compiles libnavtex_amd.so (HIP kernels for gfx950 + host C/C++)
-in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
-reference seams via oracle/Makefile.
+"""Build helper: compiles libnavtex_amd.so (HIP kernels for gfx950 + host C/C++) and its
+companion libnavtex_amd_scan.so (the band scan, navtex_amd/scan/) in-tree with hipcc, and
+-- for tests only -- the oracle library and the compiled reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
     python navtex_amd/build.py --oracle   # + oracle (and reference seams when /root/reference exists)
@@ -25,6 +25,12 @@ ARCH = "gfx950"
 
 C_SOURCES = ["nvx_sitor.c", "nvx_wav.c", "nvx_synth_host.c", "nvx_store.c"]
 HIP_SOURCES = ["nvx_cascade.hip", "nvx_fir3.hip", "nvx_demod.hip", "nvx_channelise.hip", "nvx_wideband_fused.hip", "nvx_synth.hip"]
+# the companion library (include/navtex_amd_scan.h): its own directory, objects and link; the same flags
+SCAN = PKG / "scan"
+SCAN_LIB = PKG / "libnavtex_amd_scan.so"
+SCAN_C_SOURCES = ["nvx_scan_find.c"]
+SCAN_HIP_SOURCES = ["nvx_scan.hip"]
+SCAN_CXX_SOURCES = ["nvx_scan_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp"]
 
@@ -53,12 +59,37 @@ def _stale(out: Path, deps) -> bool:
     return any(Path(d).stat().st_mtime > t for d in deps)
 
 
+def _scan_jobs(hipcc: str, force: bool):
+    """(objects, compile jobs) of the companion library: csrc headers are on its include path (FIR1's taps)."""
+    headers = list(SCAN.glob("*.h")) + list(CSRC.glob("*.h")) + list((ROOT / "include").glob("*.h")) + [Path(__file__)]
+    flags = [*COMMON, f"-I{SCAN}"]
+    objs, jobs = [], []
+    for srcs, cmd in ((SCAN_C_SOURCES, [hipcc, "-x", "c", "-std=gnu11", "-Wall", "-Wextra"]),
+                      (SCAN_HIP_SOURCES, [hipcc, f"--offload-arch={ARCH}", "-std=c++17"]),
+                      (SCAN_CXX_SOURCES, [hipcc, "-x", "hip", "--offload-arch=" + ARCH, "-std=c++17", "-Wall"])):
+        for src in srcs:
+            o = OBJ / (src + ".o")
+            if force or _stale(o, [SCAN / src] + headers):
+                jobs.append([*cmd, *flags, "-c", SCAN / src, "-o", o])
+            objs.append(o)
+    return objs, jobs
+
+
+def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
+    # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
+    tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
+    _run([hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", tmp, *libs])
+    os.replace(tmp, lib)
+
+
 def build_lib(force: bool = False) -> Path:
     from concurrent.futures import ThreadPoolExecutor
     hipcc = _hipcc()
     OBJ.mkdir(exist_ok=True)
     headers = list(CSRC.glob("*.h")) + list((ROOT / "include").glob("*.h")) + [Path(__file__)]
     objs, jobs = [], []
+    scan_objs, scan_jobs = _scan_jobs(hipcc, force)
+    jobs += scan_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -78,10 +109,9 @@ def build_lib(force: bool = False) -> Path:
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
         list(pool.map(_run, jobs))
     if force or _stale(LIB, objs):
-        # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
-        tmp = LIB.with_name(LIB.name + f".tmp{os.getpid()}")
-        _run([hipcc, "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", tmp, "-lpthread", "-ldl"])
-        os.replace(tmp, LIB)
+        _link(hipcc, LIB, objs, ["-lpthread", "-ldl"])
+    if force or _stale(SCAN_LIB, scan_objs):
+        _link(hipcc, SCAN_LIB, scan_objs, ["-lpthread", "-lm"])
     return LIB
 
 

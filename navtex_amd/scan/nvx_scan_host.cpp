@@ -1,0 +1,202 @@
+// nvx_scan_host.cpp -- the band scan's device entry points (include/navtex_amd_scan.h): argument and span checks, the
+// choice of kernel form, HIP-event timing.  The library stands alone: it shares no state with libnavtex_amd.so.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "nvx_scan_kernels.h"
+
+static thread_local char g_err[512] = "";
+
+static void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
+static void set_error(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof g_err, fmt, ap);
+    va_end(ap);
+}
+
+extern "C" const char *nvx_scan_last_error(void) { return g_err; }
+
+#define HIP_TRY(expr)                                                                      \
+    do {                                                                                   \
+        hipError_t e_ = (expr);                                                            \
+        if (e_ != hipSuccess) {                                                            \
+            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? NVX_ERR_NODEV : NVX_ERR_HIP; \
+        }                                                                                  \
+    } while (0)
+
+static int select_device(int device)
+{
+    int n = 0;
+    hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n == 0) {
+        set_error("no HIP device available (%s); the scan has no CPU path", e == hipSuccess ? "device count 0" : hipGetErrorString(e));
+        return NVX_ERR_NODEV;
+    }
+    if (device < 0 || device >= n) { set_error("device %d out of range (0..%d)", device, n - 1); return NVX_ERR_ARG; }
+    HIP_TRY(hipSetDevice(device));
+    return NVX_OK;
+}
+
+// [p, p + bytes) against the allocation the runtime knows p to lie in; no verdict (NVX_OK) for a pointer it does not know
+static int check_device_span(const void *p, size_t bytes, const char *what)
+{
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return NVX_OK; }
+    const size_t off = (size_t)((const char *)p - (const char *)base);
+    if (off > size || bytes > size - off) {
+        set_error("%s: %zu bytes from %p leave the allocation they lie in (%zu bytes from %p): the launch would fault", what, bytes, p, size, (void *)base);
+        return NVX_ERR_ARG;
+    }
+    return NVX_OK;
+}
+
+// (a * b + c) * d without wrapping; false on overflow
+static bool span_bytes(size_t a, size_t b, size_t c, size_t d, size_t *out)
+{
+    size_t t;
+    return !__builtin_mul_overflow(a, b, &t) && !__builtin_add_overflow(t, c, &t) && !__builtin_mul_overflow(t, d, out);
+}
+
+static struct ScanState {
+    std::mutex mu;
+    int form = 0;
+    bool timing = false;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool, pending;
+    double sum_ms = 0.0; uint64_t n = 0;
+} g_st;
+
+static const size_t SCRATCH_ROWS_MAX = 16384;       // form 2's frame rows: 256 MB
+
+extern "C" int nvx_scan_set_form(int form)
+{
+    if (form < 0 || form > 2) { set_error("nvx_scan_set_form: form %d (0, 1 or 2)", form); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    g_st.form = form;
+    return NVX_OK;
+}
+
+extern "C" void nvx_scan_timing(int enable) { std::lock_guard<std::mutex> lk(g_st.mu); g_st.timing = enable != 0; }
+
+extern "C" int nvx_scan_time_stats(double *sum_ms, uint64_t *launches, int reset)
+{
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    for (auto &p : g_st.pending) {
+        HIP_TRY(hipEventSynchronize(p.second));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, p.first, p.second));
+        g_st.sum_ms += ms; g_st.n++;
+        g_st.pool.push_back(p);
+    }
+    g_st.pending.clear();
+    if (sum_ms) *sum_ms = g_st.sum_ms;
+    if (launches) *launches = g_st.n;
+    if (reset) { g_st.sum_ms = 0.0; g_st.n = 0; }
+    return NVX_OK;
+}
+
+static int scan_mode(int raw_rate, int stage0_order, const char *what, int *mode)
+{
+    if (raw_rate != 0 && raw_rate != 1) { set_error("%s: raw_rate %d (0 or 1)", what, raw_rate); return NVX_ERR_ARG; }
+    if (raw_rate ? (stage0_order != 0 && stage0_order != 1 && stage0_order != 3) : (stage0_order != 0 && stage0_order != 1)) {
+        set_error("%s: stage0_order %d (1 or 3 at raw rate; 252 kS/s input has no stage 0)", what, stage0_order); return NVX_ERR_ARG;
+    }
+    *mode = !raw_rate ? NVX_SCAN_MODE_252K : (stage0_order == 3 ? NVX_SCAN_MODE_RAW3 : NVX_SCAN_MODE_RAW1);
+    return NVX_OK;
+}
+
+extern "C" int nvx_scan_resident(int device, const void *d_iq, size_t pitch_samples, size_t first_frame, int n_frames,
+                                 int n_streams, int raw_rate, int stage0_order, void *d_power, void *hip_stream)
+{
+    const char *what = "nvx_scan_resident";
+    int mode = 0;
+    int rc = scan_mode(raw_rate, stage0_order, what, &mode); if (rc != NVX_OK) return rc;
+    if (!d_iq || !d_power || n_frames < 1 || n_streams < 1 || ((uintptr_t)d_iq & 15) || ((uintptr_t)d_power & 7) || (pitch_samples & 3)) {
+        set_error("%s: bad argument (null pointer, no frames or streams, input not 16-byte aligned or pitch not a multiple of 4)", what);
+        return NVX_ERR_ARG;
+    }
+    const size_t frame_len = raw_rate ? NVX_SCAN_FRAME_RAW : NVX_SCAN_FRAME_IN;
+    // every stream's last scanned sample, in samples of its row and in bytes of the whole operand: nothing may wrap
+    size_t end_frame, row_end, in_bytes, out_bytes;
+    if (__builtin_add_overflow(first_frame, (size_t)n_frames, &end_frame) || __builtin_mul_overflow(end_frame, frame_len, &row_end) ||
+        !span_bytes((size_t)(n_streams - 1), pitch_samples, row_end, 4, &in_bytes) ||
+        !span_bytes((size_t)n_streams, NVX_SCAN_FFT, 0, sizeof(double), &out_bytes)) {
+        set_error("%s: the span of %d frames from frame %zu of %d streams at pitch %zu overflows", what, n_frames, first_frame, n_streams, pitch_samples);
+        return NVX_ERR_ARG;
+    }
+    if (n_streams > 1 && row_end > pitch_samples) {
+        set_error("%s: frames up to %zu need %zu samples per stream, the pitch is %zu", what, end_frame, row_end, pitch_samples);
+        return NVX_ERR_ARG;
+    }
+    if ((rc = select_device(device)) != NVX_OK) return rc;
+    if ((rc = check_device_span(d_iq, in_bytes, "nvx_scan_resident: input")) != NVX_OK) return rc;
+    if ((rc = check_device_span(d_power, out_bytes, "nvx_scan_resident: power rows")) != NVX_OK) return rc;
+
+    nvx_scan_args a{};
+    a.iq = (const uint32_t *)d_iq; a.pitch = pitch_samples; a.first_frame = first_frame;
+    a.n_frames = n_frames; a.n_streams = n_streams; a.mode = mode; a.power = (double *)d_power;
+
+    int form; bool timed = false;
+    std::pair<hipEvent_t, hipEvent_t> ev{ nullptr, nullptr };
+    {
+        std::lock_guard<std::mutex> lk(g_st.mu);
+        form = g_st.form;
+        if (g_st.timing) {
+            if (g_st.pool.empty()) { HIP_TRY(hipEventCreate(&ev.first)); HIP_TRY(hipEventCreate(&ev.second)); }
+            else { ev = g_st.pool.back(); g_st.pool.pop_back(); }
+            timed = true;
+        }
+    }
+    // a workgroup per stream fills the chip from about two workgroups per CU on; below that the frames are spread out too
+    const bool rows_fit = (size_t)n_streams * (size_t)n_frames <= SCRATCH_ROWS_MAX && n_streams <= 65535;
+    if (form == 0) form = n_streams >= 512 ? 1 : 2;
+    if (form == 2 && !rows_fit) form = 1;
+
+    hipStream_t s = (hipStream_t)hip_stream;
+    if (form == 2) HIP_TRY(hipMallocAsync((void **)&a.rows, (size_t)n_streams * n_frames * NVX_SCAN_FFT * sizeof(double), s));
+    if (timed) HIP_TRY(hipEventRecord(ev.first, s));
+    HIP_TRY(nvx_scan_launch(&a, form, s));
+    if (timed) {
+        HIP_TRY(hipEventRecord(ev.second, s));
+        std::lock_guard<std::mutex> lk(g_st.mu);
+        g_st.pending.push_back(ev);
+    }
+    if (form == 2) HIP_TRY(hipFreeAsync(a.rows, s));
+    return NVX_OK;
+}
+
+extern "C" int nvx_scan_iq(int device, const int16_t *iq, size_t n, int raw_rate, int stage0_order, double *power, int *frames_used)
+{
+    const char *what = "nvx_scan_iq";
+    int mode = 0;
+    int rc = scan_mode(raw_rate, stage0_order, what, &mode); if (rc != NVX_OK) return rc;
+    const size_t frame_len = raw_rate ? NVX_SCAN_FRAME_RAW : NVX_SCAN_FRAME_IN;
+    if (!iq || !power || n < frame_len || n / frame_len > 0x7fffffff) {
+        set_error("%s: bad argument (null pointer, or fewer samples than one frame of %zu)", what, frame_len);
+        return NVX_ERR_ARG;
+    }
+    const int n_frames = (int)(n / frame_len);
+    if ((rc = select_device(device)) != NVX_OK) return rc;
+    const size_t bytes = (size_t)n_frames * frame_len * 4;
+    void *d_iq = nullptr, *d_power = nullptr;
+    hipError_t e = hipMalloc(&d_iq, bytes);
+    if (e == hipSuccess) e = hipMalloc(&d_power, NVX_SCAN_FFT * sizeof(double));
+    if (e != hipSuccess) { (void)hipFree(d_iq); set_error("%s: hipMalloc failed: %s", what, hipGetErrorString(e)); return NVX_ERR_NOMEM; }
+    e = hipMemcpy(d_iq, iq, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = nvx_scan_resident(device, d_iq, (size_t)n_frames * frame_len, 0, n_frames, 1, raw_rate, stage0_order, d_power, nullptr);
+        if (rc == NVX_OK) e = hipMemcpy(power, d_power, NVX_SCAN_FFT * sizeof(double), hipMemcpyDeviceToHost);   // waits for the null stream
+    }
+    (void)hipFree(d_iq); (void)hipFree(d_power);
+    if (rc != NVX_OK) return rc;
+    if (e != hipSuccess) { set_error("%s: copy failed: %s", what, hipGetErrorString(e)); return NVX_ERR_HIP; }
+    if (frames_used) *frames_used = n_frames;
+    return NVX_OK;
+}

@@ -1,0 +1,189 @@
+"""Restatement of the band scan (include/navtex_amd_scan.h), written from the header's contract, not from the kernels:
+the oracle's stage 0 and FIR1 over the whole stream (streaming, from its reset), the slots' segments cut out of that,
+the Hann window and the explicit radix-2 stages in numpy (every fp64 operation on its own: numpy contracts nothing), the
+two-level sums, and the detector's nine rules in plain Python."""
+from __future__ import annotations
+
+import functools
+import math
+import re
+from pathlib import Path
+
+import numpy as np
+
+import oracle_binding as ob
+
+ROOT = Path(__file__).resolve().parent.parent
+HEADER = ROOT / "navtex_amd" / "scan" / "nvx_scan_table.h"
+N = 2048
+OCT = N // 8
+BIN_HZ = 63000.0 / N
+FRAME_Y1 = 20160
+SLOTS, SLOT_LEN, LEAD_IN = 9, 2240, 16
+
+DEFAULTS = dict(band_half=5, floor_half=32, guard_bins=13, shadow_bins=33, refine_half=6, refine_iters=4,
+                min_score_db=6.0, shadow_db=25.0, max_offset_hz=25000.0, dc_guard_hz=60.0, dc_max_shift_hz=120.0)
+
+
+def octant():
+    """[(cos, sin)] of 2 pi j / 2048, j = 0 .. 256, as the header holds them."""
+    body = HEADER.read_text().split("NVX_SCAN_OCTANT", 1)[1]
+    pairs = re.findall(r"\{\s*([-+0-9a-fx.p]+),\s*([-+0-9a-fx.p]+)\s*\}", body)
+    assert len(pairs) == OCT + 1
+    return [(float.fromhex(c), float.fromhex(s)) for c, s in pairs]
+
+
+@functools.lru_cache(maxsize=None)
+def table():
+    """(C, S) [2048] each: cos and sin of 2 pi j / 2048 from the octant by the exact symmetries."""
+    oc = np.array(octant())
+    j = np.arange(N)
+    q, r = j // (N // 4), j % (N // 4)
+    lo = r <= OCT
+    c = np.where(lo, oc[np.minimum(r, OCT), 0], oc[np.minimum(N // 4 - r, OCT), 1])
+    s = np.where(lo, oc[np.minimum(r, OCT), 1], oc[np.minimum(N // 4 - r, OCT), 0])
+    return (np.select([q == 0, q == 1, q == 2, q == 3], [c, -s, -c, s]),
+            np.select([q == 0, q == 1, q == 2, q == 3], [s, c, -s, -c]))
+
+
+def front(iq: np.ndarray, raw: bool, stage0_order: int = 1) -> np.ndarray:
+    """FIR1 output [n, 2] of a stream from its reset: IQ int16 [n, 2] at 2.016 MS/s (raw) or 252 kS/s."""
+    if raw:
+        x = ob.stage0_cic3(iq) if stage0_order == 3 else ob.stage0(iq)
+    else:
+        x = np.ascontiguousarray(iq, dtype=np.int16).reshape(-1, 2)
+    return ob.fir1(x)
+
+
+def segments(y1: np.ndarray, first_frame: int, n_frames: int) -> np.ndarray:
+    """[n_frames, 9, 2048, 2]: the slots' segments y1[f * 20160 + j * 2240 + 16 + n]."""
+    out = np.empty((n_frames, SLOTS, N, 2))
+    for f in range(n_frames):
+        for j in range(SLOTS):
+            o = (first_frame + f) * FRAME_Y1 + j * SLOT_LEN + LEAD_IN
+            out[f, j] = y1[o:o + N]
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def _bitrev():
+    return np.array([int(format(i, "011b")[::-1], 2) for i in range(N)])
+
+
+def window(seg: np.ndarray):
+    """v = (w I, w Q), w[n] = 0.5 - 0.5 C[n]; seg [..., 2048, 2] -> (re, im) [..., 2048]."""
+    C, _ = table()
+    w = 0.5 - 0.5 * C
+    return w * seg[..., 0], w * seg[..., 1]
+
+
+def fft(xr: np.ndarray, xi: np.ndarray):
+    """The header's transform over the last axis: bit reversal, then the stages len = 2 .. 2048, butterfly by butterfly."""
+    C, S = table()
+    lead = xr.shape[:-1]
+    xr, xi = xr[..., _bitrev()].copy(), xi[..., _bitrev()].copy()
+    ln = 2
+    while ln <= N:
+        half = ln // 2
+        j = np.arange(half) * (N // ln)
+        wr, wi = C[j], -S[j]
+        vr, vi = xr.reshape(*lead, N // ln, 2, half), xi.reshape(*lead, N // ln, 2, half)
+        ar, ai, br, bi = vr[..., 0, :], vi[..., 0, :], vr[..., 1, :], vi[..., 1, :]
+        tr = br * wr - bi * wi
+        ti = br * wi + bi * wr
+        nr, ni = np.empty_like(vr), np.empty_like(vi)
+        nr[..., 0, :], ni[..., 0, :] = ar + tr, ai + ti
+        nr[..., 1, :], ni[..., 1, :] = ar - tr, ai - ti
+        xr, xi = nr.reshape(*lead, N), ni.reshape(*lead, N)
+        ln *= 2
+    return xr, xi
+
+
+def power_row(y1: np.ndarray, first_frame: int, n_frames: int) -> np.ndarray:
+    """The scan's row [2048] of frames [first_frame, first_frame + n_frames) of the stream whose FIR1 output is y1."""
+    xr, xi = fft(*window(segments(y1, first_frame, n_frames)))
+    p = xr * xr + xi * xi                                          # [n_frames, 9, 2048]
+    total = np.zeros(N)
+    for f in range(n_frames):
+        row = np.zeros(N)
+        for j in range(SLOTS):
+            row = row + p[f, j]
+        total = total + row
+    return np.roll(total, N // 2)                                  # index i: bin (i + 1024) mod 2048
+
+
+def scan(iq: np.ndarray, raw: bool, stage0_order: int = 1, first_frame: int = 0, n_frames: int | None = None) -> np.ndarray:
+    y1 = front(iq, raw, stage0_order)
+    if n_frames is None:
+        n_frames = y1.shape[0] // FRAME_Y1 - first_frame
+    return power_row(y1, first_frame, n_frames)
+
+
+# ------------------------------------------------------------------------------------------------------------ detector
+def _circ(a: int, b: int) -> int:
+    d = abs(a - b)
+    return min(d, N - d)
+
+
+def _log_parabola(P, m: int) -> float:
+    pa, pb, pc = float(P[(m - 1) % N]), float(P[m % N]), float(P[(m + 1) % N])
+    if not (pa > 0.0 and pb > 0.0 and pc > 0.0):
+        return 0.0
+    a, b, c = math.log(pa), math.log(pb), math.log(pc)
+    den = (a - 2.0 * b) + c
+    if not den < 0.0:
+        return 0.0
+    return max(-1.0, min(1.0, (0.5 * (a - c)) / den))
+
+
+def _arg_max(P, lo: int, hi: int) -> int:
+    m = lo
+    for i in range(lo + 1, hi + 1):
+        if P[i % N] > P[m % N]:
+            m = i
+    return m
+
+
+def find(P: np.ndarray, **params):
+    """Rules 1 to 9 of the header; returns the hits as dicts, in descending score."""
+    p = dict(DEFAULTS, **params)
+    P = np.asarray(P, dtype=np.float64)
+    bh, fh = p["band_half"], p["floor_half"]
+    idx = np.arange(N)
+    B = np.zeros(N)
+    for d in range(-bh, bh + 1):
+        B = B + P[(idx + d) % N]
+    win = P[(idx[:, None] + np.arange(-fh, fh + 1)[None, :]) % N]
+    F = float(2 * bh + 1) * np.sort(win, axis=1)[:, fh]
+    cands = []
+    for i in range(N):
+        if F[i] > 0.0 and B[i] > 0.0:
+            score = 10.0 * math.log10(B[i] / F[i])
+            if score >= p["min_score_db"]:
+                cands.append((score, i))
+    cands.sort(key=lambda c: (-c[0], c[1]))
+    kept, hits = [], []
+    for score, b in cands:
+        if any(_circ(b, k) <= p["guard_bins"] for k in kept):
+            continue
+        if any(_circ(b, k) <= p["shadow_bins"] and 10.0 * math.log10(B[k] / B[b]) > p["shadow_db"] for k in kept):
+            continue
+        kept.append(b)
+        ctr = b
+        for _ in range(p["refine_iters"]):
+            num = den = 0.0
+            for d in range(-p["refine_half"], p["refine_half"] + 1):
+                v = float(P[(ctr + d) % N])
+                num = num + float(d) * v
+                den = den + v
+            if not den > 0.0:
+                break
+            ctr = int(math.floor((float(ctr) + num / den) + 0.5))
+        m_lo, m_hi = _arg_max(P, ctr - p["refine_half"], ctr - 1), _arg_max(P, ctr + 1, ctr + p["refine_half"])
+        lo, hi = float(m_lo) + _log_parabola(P, m_lo), float(m_hi) + _log_parabola(P, m_hi)
+        offset = (0.5 * (lo + hi) - float(N // 2)) * BIN_HZ
+        shift = (hi - lo) * BIN_HZ
+        if abs(offset) > p["max_offset_hz"] or (abs(offset) <= p["dc_guard_hz"] and shift < p["dc_max_shift_hz"]):
+            continue
+        hits.append(dict(offset_hz=offset, score_db=score, shift_hz=shift, band_power_db=10.0 * math.log10(B[b]), bin=b))
+    return hits
