@@ -78,6 +78,56 @@ def verify_replay(ob, buf, pitch: int, n_samples: int, raw, gpu_bits: Callable[[
     return len(streams), bad, time.perf_counter() - t0
 
 
+def verify_chains(ob, buf, pitch: int, n_samples: int, raw, masks: Sequence[int], gpu_bits: Callable[[int, int], str], ncpu: int,
+                  chunk: int = 64) -> Tuple[int, List[Tuple[int, int]], List[int], float]:
+    """EVERY chain of a resident batch against the oracle: stream s (0 .. len(masks) - 1 of buf's [stream][pitch] layout,
+    n_samples complex samples each, decoded from reset state) decodes the chains of masks[s] (1 = 518 only, 2 = 490 only,
+    3 = both); raw as ob.replay takes it (False = 252 kS/s input, True = raw rate, 3 = raw rate through the third-order
+    stage 0).  The batch is copied back a chunk of streams at a time; within a chunk the streams are grouped by mask
+    (ob.replay takes one mask per call, loops = 1).  gpu_bits(s, c) must equal the oracle's bits for every chain inside
+    masks[s] and must be "" for every chain outside it.  Returns (chains checked = chains inside their masks, bad =
+    [(stream, chain)], distinct_failures, seconds); distinct_failures: the mask-3 streams whose two oracle bit strings
+    are equal or empty -- an input that could not tell a swapped or duplicated chain from a correct one.  Nothing is
+    sampled: a caller asserts distinct_failures == [], bad == [] and the exact count."""
+    t0 = time.perf_counter()
+    masks = [int(m) for m in masks]
+    if any(m not in (1, 2, 3) for m in masks):
+        raise ValueError("verify_chains: every mask must be 1, 2 or 3")
+    n252 = n_samples // 8 if raw else n_samples
+    bad: List[Tuple[int, int]] = []
+    indistinct: List[int] = []
+    checked = 0
+    for c0 in range(0, len(masks), chunk):
+        ids = list(range(c0, min(len(masks), c0 + chunk)))
+        if pitch == n_samples:                           # one copy for the whole chunk
+            sample = buf.download(len(ids) * n_samples * 4, offset=c0 * pitch * 4, dtype=np.int16).reshape(len(ids), n_samples, 2)
+        else:
+            sample = np.empty((len(ids), n_samples, 2), dtype=np.int16)
+            for k, s in enumerate(ids):
+                sample[k] = buf.download(n_samples * 4, offset=s * pitch * 4, dtype=np.int16).reshape(-1, 2)
+        for m in (1, 2, 3):
+            sel = [k for k, s in enumerate(ids) if masks[s] == m]
+            if not sel:
+                continue
+            sub = sample if len(sel) == len(ids) else np.ascontiguousarray(sample[sel])
+            _secs, want = ob.replay(sub, len(sel), n252, raw, m, ncpu, 1)
+            for j, k in enumerate(sel):
+                s = ids[k]
+                w = want[j] if m == 3 else ((want[j], None) if m == 1 else (None, want[j]))
+                if m == 3 and (not w[0] or not w[1] or w[0] == w[1]):
+                    indistinct.append(s)
+                for c in range(2):
+                    got = gpu_bits(s, c)
+                    if w[c] is None:
+                        if got != "":
+                            bad.append((s, c))
+                    else:
+                        checked += 1
+                        if got != w[c] or not w[c]:
+                            bad.append((s, c))
+    return checked, bad, indistinct, time.perf_counter() - t0
+
+
 def spread(n_total: int, n_pick: int) -> List[int]:
     """n_pick stream indices spread over 0..n_total-1, first and last included."""
     if n_pick >= n_total:

@@ -17,6 +17,7 @@ import numpy as np
 import navtex_amd as nv
 import oracle_binding as ob
 import signals
+import tune_ref
 
 assert os.environ.get("NVX_INDEPENDENT") == "0", "run with NVX_INDEPENDENT=0: the hand-over form is the one under test"
 out = {"lib": os.environ.get("NAVTEX_AMD_LIB", "shipped"), "cases": []}
@@ -61,6 +62,52 @@ for raw, masks, order in ((False, [1, 2, 1], 1), (False, [3, 1, 3], 1), (True, [
         stale, failed, launches = p.integrity_stats()
     buf.free()
     out["cases"].append(dict(kind="resident", raw=raw, masks=masks, order=order, ok=bool(ok), stale=stale, failed=failed, launches=launches))
+
+# ---- A (tuned). ... the same launches with tuned chains (include/navtex_amd_tune.h): the table mixer starts every unit at the FIR1
+#          output index of its first pass, a pre-roll's 576 outputs earlier (behind the frame start in a frame's first
+#          third), so every repaired hand-over of the injection build pins that index at its `part`.  k per (stream,
+#          chain); a chain not named is at its nominal k (the reference mixer); chain 0 at -4480 is at chain 1's nominal
+#          k.  Each chain's carrier sits where the chain is tuned.  Against the restatement (tests/tune_ref.py).
+for raw, masks, order, tune in ((False, [3, 1, 3], 1, {(0, 0): 960, (0, 1): -2880, (1, 0): -4480, (2, 1): 4481}),
+                                (True, [3, 2, 3], 1, {(0, 0): -4480, (0, 1): 960, (1, 1): -2880, (2, 0): 4481}),
+                                (True, [3, 3, 1], 3, {(0, 0): 4481, (1, 0): -4480, (1, 1): 960, (2, 0): -2880})):
+    rate, frame = (nv.RATE_RAW, nv.FRAME_RAW) if raw else (nv.RATE_IN, nv.FRAME_IN)
+    S, F = 3, 20
+    chains = [(s, c) for s in range(S) for c in range(2) if (masks[s] >> c) & 1]
+    ks = {key: tune.get(key, tune_ref.NOMINAL[key[1]]) for key in chains}
+    assert sum(ks[key] == tune_ref.NOMINAL[key[1]] for key in chains) == 1 and len(chains) == 5
+    iqs = []
+    for s in range(S):
+        car = [dict(freq_hz=int(ks[(s, c)] * tune_ref.STEP_HZ), bits=nv.sitor_encode(signals.stream_text(740 + 2 * s + c), 10),
+                    bit_offset=(977 * (s + 1) + 331 * c) % (rate // 100) | 1, phase0=s * 7654321 + c * 13579, amplitude=5000) for c in range(2) if (masks[s] >> c) & 1]
+        iqs.append(nv.synth_host(nv.make_stream(car, seed=75 + s, noise_amp=1800), rate, F * frame))
+    buf = nv.DeviceBuffer(S * F * frame * 4)
+    for s in range(S):
+        buf.upload(iqs[s], offset=s * F * frame * 4)
+    want = {}
+    for s in range(S):
+        y1 = tune_ref.front(iqs[s], raw, order)
+        for c in range(2):
+            if (s, c) in ks:
+                want[(s, c)] = tune_ref.chain(y1, c, ks[(s, c)])
+    ok = True
+    with nv.Pipeline(n_streams=S, raw_rate=raw, chain_masks=masks, max_frames=7, char_layer=False, stage0_order=order) as p:
+        for (s, c), kc in tune.items():
+            ok = ok and p.set_carrier(s, c, kc * tune_ref.STEP_HZ) == kc * tune_ref.STEP_HZ
+        ok = ok and [p.carrier(*key)[1] for key in chains] == [key not in tune for key in chains]
+        got = {key: [] for key in chains}
+        f0 = 0
+        for nf in (7, 3, 6, 4):
+            p.process_resident(buf, F * frame, f0, nf); f0 += nf
+            p.fetch()
+            for key in got:
+                got[key].append(p.debug_y3(*key)[: nf * nv.FRAME_Y3].copy())
+        for key, parts in got.items():
+            bits = tune_ref.decode(want[key])
+            ok = ok and want[key].shape[0] == F * nv.FRAME_Y3 and np.array_equal(u64(np.concatenate(parts)), u64(want[key])) and p.bits(*key) == bits and len(bits) > 300
+        stale, failed, launches = p.integrity_stats()
+    buf.free()
+    out["cases"].append(dict(kind="resident", tuned=True, raw=raw, masks=masks, order=order, ok=bool(ok), stale=stale, failed=failed, launches=launches))
 
 # ---- B. launches that name their streams (the list kernels): random push-mode handles with silent streams
 from test_gpu_independent_streams import ragged_case
