@@ -1,6 +1,7 @@
 """Build helper: compiles libnavtex_amd.so (HIP kernels for gfx950 + host C/C++) and its
-companion libnavtex_amd_scan.so (the band scan, navtex_amd/scan/) in-tree with hipcc, and
--- for tests only -- the oracle library and the compiled reference seams via oracle/Makefile.
+companions libnavtex_amd_scan.so (the band scan, navtex_amd/scan/) and libnavtex_amd_resample.so (the resampler,
+navtex_amd/resample/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled reference seams via
+oracle/Makefile.
 
     python navtex_amd/build.py            # product library
     python navtex_amd/build.py --oracle   # + oracle (and reference seams when /root/reference exists)
@@ -31,6 +32,12 @@ SCAN_LIB = PKG / "libnavtex_amd_scan.so"
 SCAN_C_SOURCES = ["nvx_scan_find.c"]
 SCAN_HIP_SOURCES = ["nvx_scan.hip"]
 SCAN_CXX_SOURCES = ["nvx_scan_host.cpp"]
+# the second companion (include/navtex_amd_resample.h), built the same way
+RESAMPLE = PKG / "resample"
+RESAMPLE_LIB = PKG / "libnavtex_amd_resample.so"
+RESAMPLE_C_SOURCES = ["nvx_resample_design.c"]
+RESAMPLE_HIP_SOURCES = ["nvx_resample.hip"]
+RESAMPLE_CXX_SOURCES = ["nvx_resample_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp"]
 
@@ -59,20 +66,28 @@ def _stale(out: Path, deps) -> bool:
     return any(Path(d).stat().st_mtime > t for d in deps)
 
 
-def _scan_jobs(hipcc: str, force: bool):
-    """(objects, compile jobs) of the companion library: csrc headers are on its include path (FIR1's taps)."""
-    headers = list(SCAN.glob("*.h")) + list(CSRC.glob("*.h")) + list((ROOT / "include").glob("*.h")) + [Path(__file__)]
-    flags = [*COMMON, f"-I{SCAN}"]
+def _companion_jobs(hipcc: str, force: bool, src_dir: Path, c_sources, hip_sources, cxx_sources):
+    """(objects, compile jobs) of a companion library: csrc headers are on its include path (FIR1's taps)."""
+    headers = list(src_dir.glob("*.h")) + list(CSRC.glob("*.h")) + list((ROOT / "include").glob("*.h")) + [Path(__file__)]
+    flags = [*COMMON, f"-I{src_dir}"]
     objs, jobs = [], []
-    for srcs, cmd in ((SCAN_C_SOURCES, [hipcc, "-x", "c", "-std=gnu11", "-Wall", "-Wextra"]),
-                      (SCAN_HIP_SOURCES, [hipcc, f"--offload-arch={ARCH}", "-std=c++17"]),
-                      (SCAN_CXX_SOURCES, [hipcc, "-x", "hip", "--offload-arch=" + ARCH, "-std=c++17", "-Wall"])):
+    for srcs, cmd in ((c_sources, [hipcc, "-x", "c", "-std=gnu11", "-Wall", "-Wextra"]),
+                      (hip_sources, [hipcc, f"--offload-arch={ARCH}", "-std=c++17"]),
+                      (cxx_sources, [hipcc, "-x", "hip", "--offload-arch=" + ARCH, "-std=c++17", "-Wall"])):
         for src in srcs:
             o = OBJ / (src + ".o")
-            if force or _stale(o, [SCAN / src] + headers):
-                jobs.append([*cmd, *flags, "-c", SCAN / src, "-o", o])
+            if force or _stale(o, [src_dir / src] + headers):
+                jobs.append([*cmd, *flags, "-c", src_dir / src, "-o", o])
             objs.append(o)
     return objs, jobs
+
+
+def _scan_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, SCAN, SCAN_C_SOURCES, SCAN_HIP_SOURCES, SCAN_CXX_SOURCES)
+
+
+def _resample_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, RESAMPLE, RESAMPLE_C_SOURCES, RESAMPLE_HIP_SOURCES, RESAMPLE_CXX_SOURCES)
 
 
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
@@ -90,6 +105,8 @@ def build_lib(force: bool = False) -> Path:
     objs, jobs = [], []
     scan_objs, scan_jobs = _scan_jobs(hipcc, force)
     jobs += scan_jobs
+    resample_objs, resample_jobs = _resample_jobs(hipcc, force)
+    jobs += resample_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -112,6 +129,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, LIB, objs, ["-lpthread", "-ldl"])
     if force or _stale(SCAN_LIB, scan_objs):
         _link(hipcc, SCAN_LIB, scan_objs, ["-lpthread", "-lm"])
+    if force or _stale(RESAMPLE_LIB, resample_objs):
+        _link(hipcc, RESAMPLE_LIB, resample_objs, ["-lpthread", "-lm"])
     return LIB
 
 

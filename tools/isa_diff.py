@@ -1,10 +1,13 @@
 #!/usr/bin/env python3
 """Instruction-level comparison of the cascade kernels between two source trees.
 
-    python tools/isa_diff.py <git rev> [kernel regex]
+    python tools/isa_diff.py <git rev> [kernel regex] [--all]
 
 Compiles navtex_amd/csrc/nvx_cascade.hip of <git rev> and of the working tree for gfx950 (device only, -S) and compares
-the instruction streams of the kernels whose demangled names match in both (labels and comments removed).  Used in
+the instruction streams of the kernels whose demangled names match in both (labels and comments removed).  With --all:
+every device translation unit of libnavtex_amd.so (navtex_amd/csrc/*.hip) and of the scan library (navtex_amd/scan/*.hip),
+which is how a feature that lives in a library of its own shows that it left those kernels alone
+(profiles/resample_isa_identical.txt).  Used in
 round 5 to show that pruning the A/B alternates out of the roofline kernel changed no instruction of the kernels that
 ship (profiles/r05/a0_prune_isa_identical.txt); hipcc cross-compiles, no GPU needed."""
 import re
@@ -16,14 +19,20 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent.parent
 
 
-def compile_tree(tree: Path, out: Path) -> dict:
+def compile_tree(tree: Path, out: Path, everything: bool = False) -> dict:
     csrc = tree / "navtex_amd" / "csrc"
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", f"-I{tree / 'include'}", f"-I{csrc}",
-                    "--cuda-device-only", "-S", str(csrc / "nvx_cascade.hip"), "-o", str(out)], check=True, capture_output=True)
-    text = out.read_text()
+    sources = [csrc / "nvx_cascade.hip"]
+    if everything:
+        sources = sorted(csrc.glob("*.hip")) + sorted((tree / "navtex_amd" / "scan").glob("*.hip"))
+    text = ""
+    for src in sources:
+        subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", f"-I{tree / 'include'}", f"-I{csrc}",
+                        f"-I{src.parent}", "--cuda-device-only", "-S", str(src), "-o", str(out)], check=True, capture_output=True)
+        text += out.read_text()
     kernels = {}
-    for m in re.finditer(r"^(_Z\w+):.*?s_endpgm", text, flags=re.S | re.M):
-        name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
+    for sym in re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, flags=re.M):         # the kernels, not the data symbols
+        m = re.search(rf"^{re.escape(sym)}:.*?s_endpgm", text, flags=re.S | re.M)
+        name = subprocess.run(["c++filt", sym], capture_output=True, text=True).stdout.strip()
         name = re.sub(r"^void |\(.*$", "", name)
         body = [re.sub(r"\.LBB\d+_\d+", "L", re.sub(r";.*", "", l)).strip() for l in m.group(0).splitlines()
                 if l.startswith("\t") and not l.strip().startswith((".", ";"))]
@@ -37,15 +46,17 @@ def canonical(name: str) -> str:
 
 
 def main():
-    rev = sys.argv[1]
-    pat = re.compile(sys.argv[2] if len(sys.argv) > 2 else ".")
+    everything = "--all" in sys.argv
+    args = [a for a in sys.argv[1:] if a != "--all"]
+    rev = args[0]
+    pat = re.compile(args[1] if len(args) > 1 else ".")
     with tempfile.TemporaryDirectory() as td:
         old = Path(td) / "old"
         old.mkdir()
-        tar = subprocess.run(["git", "-C", str(ROOT), "archive", rev, "navtex_amd/csrc", "include"], check=True, capture_output=True).stdout
+        tar = subprocess.run(["git", "-C", str(ROOT), "archive", rev, "navtex_amd/csrc", *(["navtex_amd/scan"] if everything else []), "include"], check=True, capture_output=True).stdout
         subprocess.run(["tar", "x", "-C", str(old)], input=tar, check=True)
-        a = {canonical(k): v for k, v in compile_tree(old, Path(td) / "a.s").items()}
-        b = compile_tree(ROOT, Path(td) / "b.s")
+        a = {canonical(k): v for k, v in compile_tree(old, Path(td) / "a.s", everything).items()}
+        b = compile_tree(ROOT, Path(td) / "b.s", everything)
     print(f"{rev}: {len(a)} kernels; working tree: {len(b)} kernels")
     same = True
     for name in sorted(b):
