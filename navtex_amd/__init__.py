@@ -14,11 +14,11 @@ import numpy as np
 
 from . import _native as N
 from ._native import (CHAIN_490, CHAIN_518, FRAME_BITS, FRAME_IN, FRAME_RAW, FRAME_Y3, RATE_IN, RATE_RAW,
-                      NvxError, lib)
+                      SOFT_DECODE, SOFT_KEEP, NvxError, lib)
 
 __all__ = ["Pipeline", "Group", "Capture", "Sitor", "sitor_encode", "make_stream", "synth_host", "synth_device", "device_count",
            "DeviceBuffer", "channelise", "channelise_time_stats", "Store", "wav_write", "wav_read", "NvxError", "lib",
-           "CHAIN_518", "CHAIN_490", "FRAME_BITS", "FRAME_IN", "FRAME_RAW", "FRAME_Y3", "RATE_IN", "RATE_RAW"]
+           "CHAIN_518", "CHAIN_490", "SOFT_DECODE", "SOFT_KEEP", "FRAME_BITS", "FRAME_IN", "FRAME_RAW", "FRAME_Y3", "RATE_IN", "RATE_RAW"]
 
 
 def device_count() -> int:
@@ -38,7 +38,7 @@ def sitor_encode(text: str, n_phasing: int = 40) -> str:
 class Sitor:
     """Host character layer (nvx_sitor_*): bits in, (bbbb, message, freq) out."""
 
-    def __init__(self, freq: int = 518, trace: bool = False):
+    def __init__(self, freq: int = 518, trace: bool = False, soft: bool = False):
         self.messages: List[Tuple[int, str, str]] = []
         self.trace_text: List[str] = []
         self._cb = N.SITOR_MSG_FN(lambda u, b, m, f: self.messages.append((f, b.decode("latin1"), m.decode("latin1"))))
@@ -46,10 +46,21 @@ class Sitor:
         if trace:
             self._tcb = N.SITOR_TRACE_FN(lambda u, t: self.trace_text.append(t.decode("latin1")))
             lib.nvx_sitor_set_trace(self._h, self._tcb, None)
+        if soft:
+            self.set_soft(True)
 
     def feed(self, bits: str) -> None:
         b = bits.encode("ascii")
         lib.nvx_sitor_receive_bits(self._h, b, len(b))
+
+    def set_soft(self, on: bool = True) -> None:
+        """The soft combining rule on or off (nvx_sitor_set_soft, include/navtex_amd_soft.h)."""
+        lib.nvx_sitor_set_soft(self._h, int(on))
+
+    def feed_soft(self, soft) -> None:
+        """Bits with their soft values (nvx_sitor_receive_soft): float32, > 0 = 'B'."""
+        v = np.ascontiguousarray(soft, dtype=np.float32)
+        lib.nvx_sitor_receive_soft(self._h, N.as_ptr(v), v.size)
 
     def trace(self) -> str:
         return "".join(self.trace_text)
@@ -186,6 +197,31 @@ class HandleStats:
         r = N.SignalReport()
         N.check(lib.nvx_signal_report_read(self._h, stream, chain, C.byref(r), int(reset)), "nvx_signal_report_read")
         return {f: getattr(r, f) for f, _ in N.SignalReport._fields_}
+
+    def enable_soft(self, mode: int = N.SOFT_DECODE, on_message: Optional[Callable[[int, int, str, str], None]] = None) -> None:
+        """Soft decoding (nvx_enable_soft, include/navtex_amd_soft.h): mode 0 off, SOFT_DECODE, SOFT_DECODE | SOFT_KEEP.  The soft
+        character layers' messages go to on_message(stream, freq, bbbb, text) when given, else to self.soft_messages."""
+        if not hasattr(self, "soft_messages"):
+            self.soft_messages: List[Tuple[int, int, str, str]] = []
+        if mode:
+            sink = on_message or (lambda s, f, b, t: self.soft_messages.append((s, f, b, t)))
+            self._soft_cb = N.MESSAGE_FN(lambda u, s, b, m, f: sink(s, f, b.decode("latin1"), m.decode("latin1")))
+            N.check(lib.nvx_set_soft_message_fn(self._h, self._soft_cb, None), "nvx_set_soft_message_fn")
+        N.check(lib.nvx_enable_soft(self._h, int(mode)), "nvx_enable_soft")
+
+    def soft_values(self, stream: int = 0, chain: int = 0) -> np.ndarray:
+        """The soft values not polled yet on (stream, chain) as float32 (nvx_poll_soft; needs SOFT_KEEP): consumed, like poll_bits."""
+        parts, cap = [], 1 << 14
+        while True:
+            buf = np.empty(cap, dtype=np.float32)
+            n = lib.nvx_poll_soft(self._h, stream, chain, N.as_ptr(buf), cap)
+            parts.append(buf[:n])
+            if n < cap:
+                break
+        return np.concatenate(parts)
+
+    def soft_count(self, stream: int = 0, chain: int = 0) -> int:
+        return int(lib.nvx_soft_count(self._h, stream, chain))
 
     def set_carrier(self, stream: int, chain: int, offset_hz: float) -> float:
         """Tune (stream, chain) to offset_hz from its stream's centre (nvx_set_carrier, include/navtex_amd_tune.h): from the

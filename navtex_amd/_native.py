@@ -18,6 +18,7 @@ OK, ERR_ARG, ERR_NODEV, ERR_HIP, ERR_NOMEM, ERR_STATE, ERR_IO = 0, -1, -2, -3, -
 RATE_RAW, RATE_IN = 2016000, 252000
 FRAME_BITS, FRAME_IN, FRAME_RAW, FRAME_Y3 = 32, 80640, 645120, 288
 CHAIN_518, CHAIN_490 = 1, 2
+SOFT_DECODE, SOFT_KEEP = 1, 2                                                        # include/navtex_amd_soft.h
 TUNE_N, TUNE_STEP_HZ, TUNE_MAX_HZ, TUNE_NOMINAL_K = 20160, 3.125, 25000.0, 4480     # include/navtex_amd_tune.h
 
 MESSAGE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_int)
@@ -104,6 +105,9 @@ def _load() -> C.CDLL:
         "nvx_debug_y3": (sz, [vp, i, i, vp, sz]), "nvx_debug_dphi": (sz, [vp, i, i, vp, sz]),
         "nvx_debug_timing": (sz, [vp, i, i, vp, vp, vp, sz]),
         "nvx_enable_signal_report": (i, [vp, i]), "nvx_signal_report_read": (i, [vp, i, i, C.POINTER(SignalReport), i]),
+        "nvx_enable_soft": (i, [vp, i]), "nvx_set_soft_message_fn": (i, [vp, MESSAGE_FN, vp]),
+        "nvx_poll_soft": (sz, [vp, i, i, vp, sz]), "nvx_soft_count": (C.c_uint64, [vp, i, i]),
+        "nvx_sitor_set_soft": (None, [vp, i]), "nvx_sitor_receive_soft": (None, [vp, vp, sz]),
         "nvx_set_carrier": (i, [vp, i, i, C.c_double, C.POINTER(C.c_double)]),
         "nvx_get_carrier": (i, [vp, i, i, C.POINTER(C.c_double), C.POINTER(i)]),
         "nvx_group_set_carrier": (i, [vp, i, i, C.c_double, C.POINTER(C.c_double)]),

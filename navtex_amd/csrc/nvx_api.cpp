@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cmath>
 #include "navtex_amd_signal.h"
+#include "navtex_amd_soft.h"
 #include "navtex_amd_tune.h"
 #include "nvx_fsm.h"
 
@@ -70,7 +71,8 @@ static void sitor_sink_impl(nvx_handle *h, int slot, const char *bbbb, const cha
 static void sitor_sink(void *user, const char *bbbb, const char *message, int freq)
 {
     SinkCtx *c = (SinkCtx *)user;
-    sitor_sink_impl(c->h, c->slot, bbbb, message, freq);
+    if (c->soft) c->h->slots[c->slot].soft_outbox.push_back(Message{ bbbb, message, freq });
+    else sitor_sink_impl(c->h, c->slot, bbbb, message, freq);
 }
 
 extern "C" void nvx_config_default(nvx_config *c)
@@ -118,6 +120,27 @@ static void free_signal(nvx_handle *h)
     h->sig_on = false; h->sig_stride = 0;
 }
 
+// nvx_enable_soft's buffers and state, made together and released together: the soft character layers and the kept
+// values go with them
+static void free_soft(nvx_handle *h)
+{
+    (void)hipFree(h->d_soft_pos); h->d_soft_pos = nullptr;
+    for (auto &r : h->res) {
+        (void)hipFree(r.d_soft); r.d_soft = nullptr;
+        (void)hipHostFree(r.h_soft); r.h_soft = nullptr;
+        r.soft = false;                                  // (a launch still to be collected brings no values any more)
+    }
+    for (auto &s : h->slots) {
+        if (s.soft_sitor) { nvx_sitor_free(s.soft_sitor); s.soft_sitor = nullptr; }
+        s.soft_outbox.clear();
+        std::vector<float>().swap(s.soft);
+        s.soft_base = s.soft_polled = 0; s.soft_count = 0;
+    }
+    for (auto it = h->sinks.begin(); it != h->sinks.end();)             // the soft layers' sink contexts
+        if ((*it)->soft) { delete *it; it = h->sinks.erase(it); } else ++it;
+    h->soft_mode = 0; h->soft_cap = 0;
+}
+
 static void free_handle(nvx_handle *h)
 {
     if (!h) return;
@@ -127,6 +150,7 @@ static void free_handle(nvx_handle *h)
     snprintf(g_err, sizeof g_err, "%s", err.c_str());
     free_debug(h);
     free_signal(h);
+    free_soft(h);
     for (auto it = h->made.rbegin(); it != h->made.rend(); ++it) {      // the streams, made first, go last
         switch (it->first) {
         case HipRes::stream: (void)hipStreamDestroy((hipStream_t)it->second); break;
@@ -311,6 +335,8 @@ static int clear_streams_locked(nvx_handle *h, int first, int last)
         s.bits.clear(); s.base = 0; s.polled = 0;
         s.sig = SigSums{};
         if (s.sitor) nvx_sitor_reset(s.sitor);
+        if (s.soft_sitor) nvx_sitor_reset(s.soft_sitor);
+        s.soft.clear(); s.soft_base = 0; s.soft_polled = 0; s.soft_count = 0;
     }
     const int64_t now = nvx_now_ns();
     for (int s = first; s < last; s++) {
@@ -439,6 +465,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     da.bits = r.d_bits; da.bits_cap = h->bits_cap; da.nbits = r.d_nbits; da.dphi = h->d_dphi; da.ties = h->d_ties;
     da.corr = h->d_corr; da.csum = h->d_csum;
     da.sig = h->sig_on ? r.d_sig : nullptr; da.sig_part = h->d_sig_part; da.sig_stride = h->sig_stride;
+    da.soft = h->soft_mode ? r.d_soft : nullptr; da.soft_cap = std::min(h->soft_cap, n3_full / 8 + 8); da.soft_pos = h->d_soft_pos;
 
     // cascade on `st`: it may not overwrite y3[yb] before the demodulator of two launches ago has read it
     if (h->demod_pending[yb]) HIP_TRY(hipStreamWaitEvent(st, h->demod_done[yb], 0));
@@ -487,17 +514,25 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     if (r.timed) HIP_TRY(hipEventRecord(r.ev[2], sd));
     HIP_TRY(nvx_launch_demod_front(&da, sd));
     if (r.timed) HIP_TRY(hipEventRecord(r.ev[3], sd));
-    HIP_TRY(hipEventRecord(h->demod_done[yb], sd));      // y3[yb] consumed
+    if (!da.soft) HIP_TRY(hipEventRecord(h->demod_done[yb], sd));      // y3[yb] consumed
     h->demod_pending[yb] = true;
     // FSM + bit download behind the front
     if (r.timed) HIP_TRY(hipEventRecord(r.ev[4], sd));
     HIP_TRY(nvx_launch_demod_fsm(&da, sd));
     if (r.timed) HIP_TRY(hipEventRecord(r.ev[5], sd));
+    // (soft values: the FSM kernel reads the bits' windows from y3[yb] too -- consumed only now; the cascade that waits for
+    // this is the one after the next, which starts long after this FSM has run beside the next)
+    if (da.soft) HIP_TRY(hipEventRecord(h->demod_done[yb], sd));
     HIP_TRY(hipMemcpyAsync(h->h_ties, h->d_ties, sizeof(nvx_tie_stats), hipMemcpyDeviceToHost, sd));
     HIP_TRY(hipMemcpyAsync(r.h_nbits, r.d_nbits, (size_t)h->n_slots * sizeof(int), hipMemcpyDeviceToHost, sd));
     HIP_TRY(hipMemcpyAsync(r.h_bits, r.d_bits, (size_t)h->n_slots * h->bits_cap, hipMemcpyDeviceToHost, sd));
     if (da.sig) HIP_TRY(hipMemcpyAsync(r.h_sig, r.d_sig, (size_t)h->n_slots * sizeof(nvx_sig_rec), hipMemcpyDeviceToHost, sd));
     r.sig = da.sig != nullptr;
+    // 4 bytes per bit: the rows are as long as this launch's bits can reach (a bit takes at least eight samples; bits_cap
+    // above), so that one copy moves them all
+    if (da.soft) HIP_TRY(hipMemcpyAsync(r.h_soft, r.d_soft, (size_t)h->n_slots * da.soft_cap * sizeof(float), hipMemcpyDeviceToHost, sd));
+    r.soft_pitch = da.soft_cap;
+    r.soft = da.soft != nullptr;
     HIP_TRY(hipEventRecord(r.done, sd));
     HIP_TRY(hipEventRecord(h->launch_done, sd));                    // sd has waited for st's last operation
     h->launch_done_valid = true; h->last_launch_stream = st;
@@ -599,9 +634,10 @@ int nvx_collect_locked(nvx_handle *h, uint64_t upto)
                 HIP_TRY(hipEventElapsedTime(&h->ms[1], r.ev[2], r.ev[3]));
                 HIP_TRY(hipEventElapsedTime(&fsm_ms, r.ev[4], r.ev[5]));
                 h->ms[1] += fsm_ms;                       // "demodulator" = front + FSM
+                h->ms[3] = fsm_ms;                        // ... and the FSM kernel alone
                 h->ms[2] = 0.f;
                 if (h->d_y2[0]) HIP_TRY(hipEventElapsedTime(&h->ms[2], r.ev[6], r.ev[7]));
-                h->ms_sum[0] += h->ms[0]; h->ms_sum[1] += h->ms[1]; h->ms_sum[2] += h->ms[2]; h->ms_count++;
+                h->ms_sum[0] += h->ms[0]; h->ms_sum[1] += h->ms[1]; h->ms_sum[2] += h->ms[2]; h->ms_sum[3] += h->ms[3]; h->ms_count++;
             }
             std::atomic<int> bad_slot{ -1 };
             // the chains of this launch: every slot, or (a launch with a participant list) the 2 * per_part slots of each
@@ -614,12 +650,25 @@ int nvx_collect_locked(nvx_handle *h, uint64_t upto)
                     Slot &s = h->slots[i];
                     if (!s.active) continue;
                     int n = r.h_nbits[i];
-                    if (n < 0 || n > h->bits_cap * 8) { bad_slot = i; continue; }
+                    if (n < 0 || n > h->bits_cap * 8 || (r.soft && n > r.soft_pitch)) { bad_slot = i; continue; }
                     const uint32_t *pw = (const uint32_t *)(r.h_bits + (size_t)i * h->bits_cap);
                     const size_t at = s.bits.size();
                     s.bits.resize(at + (size_t)n);
                     for (int b = 0; b < n; b++) s.bits[at + b] = ((pw[b >> 5] >> (b & 31)) & 1u) ? 'B' : 'Y';
                     if (s.sitor) nvx_sitor_receive_bits(s.sitor, s.bits.data() + at, (size_t)n);
+                    if (r.soft) {                                               // the soft values move with the bits, one per bit
+                        const float *v = r.h_soft + (size_t)i * r.soft_pitch;
+                        if (s.soft_sitor) nvx_sitor_receive_soft(s.soft_sitor, v, (size_t)n);
+                        s.soft_count += (uint64_t)n;
+                        if (h->soft_mode & NVX_SOFT_KEEP) {
+                            s.soft.insert(s.soft.end(), v, v + n);
+                            if (s.soft.size() > 2 * h->bit_history) {          // the rule of the bits below
+                                const size_t drop = s.soft.size() - h->bit_history;
+                                s.soft.erase(s.soft.begin(), s.soft.begin() + (ptrdiff_t)drop);
+                                s.soft_base += drop;
+                            }
+                        }
+                    }
                     if (r.sig) {                                                // the signal report moves with the bits
                         const nvx_sig_rec &q = r.h_sig[i];
                         SigSums &g = s.sig;
@@ -665,6 +714,11 @@ int nvx_collect_locked(nvx_handle *h, uint64_t upto)
                 return NVX_ERR_HIP;
             }
             for (int i = 0; i < h->n_slots; i++) if (!h->slots[i].outbox.empty()) deliver_outbox(h, i / 2, h->slots[i]);
+            for (int i = 0; i < h->n_slots; i++) {       // the soft layers' messages: to their own sink, or nowhere
+                Slot &s = h->slots[i];
+                if (h->soft_fn) for (auto &m : s.soft_outbox) h->soft_fn(h->soft_user, i / 2, m.bbbb.c_str(), m.text.c_str(), m.freq);
+                s.soft_outbox.clear();
+            }
             if (h->n_arrival) {
                 // live path: the frames of this launch are now decoded, pollable and their messages delivered
                 const int64_t now = nvx_now_ns();
@@ -751,14 +805,14 @@ extern "C" size_t nvx_poll_bits(nvx_handle *h, int stream, int chain, char *out,
 }
 
 extern "C" void nvx_enable_timing(nvx_handle *h, int enabled) { if (h) h->timing = enabled != 0; }
-extern "C" float nvx_last_kernel_ms(nvx_handle *h, int which) { return (h && which >= 0 && which < 3) ? h->ms[which] : -1.f; }
+extern "C" float nvx_last_kernel_ms(nvx_handle *h, int which) { return (h && which >= 0 && which < 4) ? h->ms[which] : -1.f; }
 extern "C" int nvx_kernel_time_stats(nvx_handle *h, int which, double *sum_ms, uint64_t *launches, int reset)
 {
-    if (!h || which < 0 || which > 2) return NVX_ERR_ARG;
+    if (!h || which < 0 || which > 3) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     if (sum_ms) *sum_ms = h->ms_sum[which];
     if (launches) *launches = h->ms_count;
-    if (reset) { h->ms_sum[0] = h->ms_sum[1] = h->ms_sum[2] = 0.0; h->ms_count = 0; }
+    if (reset) { h->ms_sum[0] = h->ms_sum[1] = h->ms_sum[2] = h->ms_sum[3] = 0.0; h->ms_count = 0; }
     return NVX_OK;
 }
 
@@ -841,6 +895,78 @@ extern "C" int nvx_enable_signal_report(nvx_handle *h, int on)
     h->sig_stride = stride;
     h->sig_on = true;
     return NVX_OK;
+}
+
+// Soft decoding (navtex_amd_soft.h).  As the signal reports: the handle's work is waited for, so a launch is soft or it
+// is not.  A change between the two "on" modes keeps buffers, layers and count; the kept values go when KEEP goes.
+extern "C" int nvx_enable_soft(nvx_handle *h, int mode)
+{
+    if (!h) { nvx_set_error("nvx_enable_soft: null handle"); return NVX_ERR_ARG; }
+    if (mode != 0 && mode != NVX_SOFT_DECODE && mode != (NVX_SOFT_DECODE | NVX_SOFT_KEEP)) { nvx_set_error("nvx_enable_soft: mode %d (0, NVX_SOFT_DECODE, NVX_SOFT_DECODE | NVX_SOFT_KEEP)", mode); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->poisoned) return nvx_poisoned_error(h);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
+    if (!mode) { free_soft(h); return NVX_OK; }
+    if (!h->soft_mode) {
+        const int cap = h->bits_cap * 8;                 // a launch's bits fill at most a row of the bit buffer
+        const size_t row_bytes = (size_t)h->n_slots * cap * sizeof(float);
+        hipError_t e = hipMalloc(&h->d_soft_pos, (size_t)(h->y3_cap / 9) * h->n_slots * sizeof(unsigned short));
+        for (auto &r : h->res) {
+            if (e == hipSuccess) e = hipMalloc(&r.d_soft, row_bytes);
+            if (e == hipSuccess) e = hipHostMalloc((void **)&r.h_soft, row_bytes, hipHostMallocDefault);
+        }
+        if (e != hipSuccess) {
+            free_soft(h);
+            nvx_set_error("nvx_enable_soft: allocation failed: %s", hipGetErrorString(e));
+            return e == hipErrorOutOfMemory ? NVX_ERR_NOMEM : NVX_ERR_HIP;
+        }
+        h->soft_cap = cap;
+        if (h->cfg.char_layer)                           // a soft layer beside every hard one
+            for (int i = 0; i < h->n_slots; i++) {
+                Slot &s = h->slots[i];
+                if (!s.active) continue;
+                SinkCtx *ctx = new SinkCtx{ h, i / 2, i, true };
+                h->sinks.push_back(ctx);
+                s.soft_sitor = nvx_sitor_new(s.label, sitor_sink, ctx);
+                nvx_sitor_set_soft(s.soft_sitor, 1);
+            }
+    }
+    if (!(mode & NVX_SOFT_KEEP))
+        for (auto &s : h->slots) { s.soft_base += s.soft.size(); std::vector<float>().swap(s.soft); }
+    else if (!(h->soft_mode & NVX_SOFT_KEEP))
+        for (auto &s : h->slots) { s.soft_base = (size_t)s.soft_count; s.soft_polled = s.soft_base; }     // kept from here on
+    h->soft_mode = mode;
+    return NVX_OK;
+}
+
+extern "C" int nvx_set_soft_message_fn(nvx_handle *h, nvx_message_fn fn, void *user)
+{
+    if (!h) { nvx_set_error("nvx_set_soft_message_fn: null handle"); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->poisoned) return nvx_poisoned_error(h);
+    h->soft_fn = fn; h->soft_user = user;
+    return NVX_OK;
+}
+
+extern "C" size_t nvx_poll_soft(nvx_handle *h, int stream, int chain, float *out, size_t cap)
+{
+    if (!h || !out || stream < 0 || stream >= h->n_streams || chain < 0 || chain > 1) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!(h->soft_mode & NVX_SOFT_KEEP)) return 0;
+    Slot &s = h->slots[2 * stream + chain];
+    if (s.soft_polled < s.soft_base) s.soft_polled = s.soft_base;       // the reader fell more than the history behind
+    const size_t n = std::min(cap, s.soft_base + s.soft.size() - s.soft_polled);
+    if (n) memcpy(out, s.soft.data() + (s.soft_polled - s.soft_base), n * sizeof(float));
+    s.soft_polled += n;
+    return n;
+}
+
+extern "C" uint64_t nvx_soft_count(nvx_handle *h, int stream, int chain)
+{
+    if (!h || stream < 0 || stream >= h->n_streams || chain < 0 || chain > 1) return 0;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return h->slots[2 * stream + chain].soft_count;
 }
 
 // Carrier tuning (navtex_amd_tune.h).  The launches in flight keep the k they were launched with: the handle's work is

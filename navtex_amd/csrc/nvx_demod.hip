@@ -86,8 +86,9 @@ __device__ __forceinline__ double front_dphi(double2 s, double2 p)
 // mark/space decision for a window ENDING at sample t, decoder.C:115-132: float*float product, double*float product,
 // double sum, accumulate in double, round to float -- five samples, filter index 0..4
 // hi / lo: the larger and the smaller of the two energies compared (the signal report's matched-filter contrast)
-__device__ __forceinline__ unsigned char front_decision(double2 w0, double2 w1, double2 w2, double2 w3, double2 w4,       // w_i = sample t - 4 + i
-                                                        float &hi, float &lo)
+// the two energies of that window, decoder.C:115-132 as written (mixed float / double, nothing contracted)
+__device__ __forceinline__ void front_energies(double2 w0, double2 w1, double2 w2, double2 w3, double2 w4,                // w_i = sample t - 4 + i
+                                               float &Brot, float &Yrot)
 {
     float BR = 0.0f, BI = 0.0f, YR = 0.0f, YI = 0.0f;
 #pragma unroll
@@ -100,8 +101,13 @@ __device__ __forceinline__ unsigned char front_decision(double2 w0, double2 w1, 
         BR = (float)((double)BR + ((double)((float)sampleR * fR) + sampleI * (double)fI));
         BI = (float)((double)BI + ((double)((float)(-sampleR) * fI) + sampleI * (double)fR));
     }
-    const float Brot = BR * BR + BI * BI;
-    const float Yrot = YR * YR + YI * YI;
+    Brot = BR * BR + BI * BI;
+    Yrot = YR * YR + YI * YI;
+}
+__device__ __forceinline__ unsigned char front_decision(double2 w0, double2 w1, double2 w2, double2 w3, double2 w4, float &hi, float &lo)
+{
+    float Brot, Yrot;
+    front_energies(w0, w1, w2, w3, w4, Brot, Yrot);
     const bool b = Brot > Yrot;
     hi = b ? Brot : Yrot; lo = b ? Yrot : Brot;
     return b ? 1 : 0;
@@ -436,29 +442,52 @@ __global__ __launch_bounds__(NVX_FRONT_THREADS) void nvx_demod_front_tiles(nvx_d
     }
 }
 
+// Soft values (navtex_amd_soft.h; SOFT = a.soft != NULL, a form of its own so that without them the kernel is the code it
+// was): soft = Brot - Yrot of a decided bit's own window.  Only this kernel knows where a bit's window ends, and the
+// energies of a window are a pure function of five samples, so the walk only NOTES per period which samples it decided on
+// (one 16-bit NVX_FSM_POS word, eight per 16-byte store) and a second pass evaluates those windows from y3 -- loads whose
+// addresses depend on the notes alone, so they pipeline instead of lengthening the walk's dependent chain.  A window that
+// ends on local sample t < 4 reaches into the previous launch: the four samples the demodulator state carries (DS_Y3 of
+// the block the launch READS; zeros after a reset).
+#ifndef NVX_SOFT_INFLIGHT
+#define NVX_SOFT_INFLIGHT 2                                  /* windows of the second pass in flight per lane (1, 2, 4 or 8) */
+#endif
+template <bool HIST>
+__device__ __forceinline__ float fsm_soft_at(const double2 *y3, const double *hist, int t)
+{
+    double2 w[5];
+#pragma unroll
+    for (int i = 0; i < 5; i++) w[i] = HIST ? y3_at(y3, hist, t - 4 + i) : y3[t - 4 + i];
+    float Brot, Yrot;
+    front_energies(w[0], w[1], w[2], w[3], w[4], Brot, Yrot);
+    return Brot - Yrot;
+}
+// the values of bit period m (note p) behind the j values the row holds already; returns the new count
+__device__ __forceinline__ int fsm_soft_period(const double2 *y3, const double *hist, int m, unsigned p, float *row, int cap, int j)
+{
+    const int n = NVX_FSM_POS_N(p);
+    if (n >= 1) { const float v = fsm_soft_at<true>(y3, hist, 9 * m + NVX_FSM_POS_K1(p)); if (j < cap) row[j] = v; j++; }
+    if (n == 2) { const float v = fsm_soft_at<true>(y3, hist, 9 * m + NVX_FSM_POS_K2(p)); if (j < cap) row[j] = v; j++; }
+    return j;
+}
+
 // Sequential part: the timing slew limiter (decoder.C:217-249) and the bit FSM
 // (decoder.C:62-137), integers only, one lane per chain.  Both are stated per
 // sample in nvx_fsm.h; the kernel advances a whole bit period at a time with
 // the transition table generated from that statement (29 KB, copied to LDS):
 // the dependent chain per period is the slew rule, one LDS lookup and a few
 // bit operations instead of nine sample steps.
-__global__ __launch_bounds__(64) void nvx_demod_fsm(nvx_demod_args a)
+template <bool SOFT>
+__device__ __forceinline__ void fsm_chain(const nvx_demod_args &a, const uint32_t *s_tab)
 {
-    __shared__ uint32_t s_tab[NVX_FSM_TABLE_ALLOC];
-    {
-        const uint4 *src = (const uint4 *)a.fsm_table;
-        uint4 *dst = (uint4 *)s_tab;
-        for (int i = threadIdx.x; i < NVX_FSM_TABLE_ALLOC / 4; i += 64) dst[i] = src[i];
-    }
-    __syncthreads();
     int slot = blockIdx.x * 64 + threadIdx.x;
     const int nc = a.n_slots;
-    int n3 = a.n3;
+    int n3 = a.n3, parity = 0;
     if (a.part) {                                        // the slots of the launch's participants, as in the front kernel
         const int per = 2 * a.per_part, e = slot / per;
         if (e >= a.n_part) return;
         slot = a.part[e].stream * per + (slot - e * per);
-        n3 = a.part[e].n3;
+        n3 = a.part[e].n3; parity = a.part[e].parity;
     }
     if (slot >= nc) return;
     if (!a.slot_active[slot]) return;
@@ -482,6 +511,7 @@ __global__ __launch_bounds__(64) void nvx_demod_fsm(nvx_demod_args a)
     const unsigned short *wrow = a.words + (size_t)slot * (a.y3_cap / 9);
     const uint4 *words = (const uint4 *)wrow;
     uint4 wnext = words[0];
+    unsigned short *prow = SOFT ? a.soft_pos + (size_t)slot * (a.y3_cap / 9) : nullptr;    // the walk's notes, a row like wrow
 
     int m0 = 0;
     for (; m0 + 8 <= periods; m0 += 8) {
@@ -489,12 +519,18 @@ __global__ __launch_bounds__(64) void nvx_demod_fsm(nvx_demod_args a)
         if (m0 + 16 <= periods) wnext = words[m0 / 8 + 1];
         const unsigned wcur[8] = { wv.x & 0xffffu, wv.x >> 16, wv.y & 0xffffu, wv.y >> 16,
                                    wv.z & 0xffffu, wv.z >> 16, wv.w & 0xffffu, wv.w >> 16 };
+        unsigned pcur[8];
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             int n;
-            const unsigned b = nvx_fsm_period(s_tab, wcur[i], &r, &n);
+            const unsigned b = nvx_fsm_period_pos(s_tab, wcur[i], &r, &n, &pcur[i]);
             acc |= (unsigned long long)(b & ((1u << n) - 1u)) << nacc;
             nacc += n;
+        }
+        if (SOFT) {
+            uint4 pv;
+            pv.x = pcur[0] | pcur[1] << 16; pv.y = pcur[2] | pcur[3] << 16; pv.z = pcur[4] | pcur[5] << 16; pv.w = pcur[6] | pcur[7] << 16;
+            ((uint4 *)prow)[m0 / 8] = pv;
         }
         // at most 10 bits per 8 periods: one store check per group
         if (nacc >= 32) {
@@ -506,15 +542,20 @@ __global__ __launch_bounds__(64) void nvx_demod_fsm(nvx_demod_args a)
     // last period one at a time, by the per-sample rule the table is generated from (nvx_fsm.h; decoder.C:62-137, 202-249)
     for (; m0 < periods; m0++) {
         int n;
-        const unsigned b = nvx_fsm_period(s_tab, wrow[m0], &r, &n);
+        unsigned pos;
+        const unsigned b = nvx_fsm_period_pos(s_tab, wrow[m0], &r, &n, &pos);
+        if (SOFT) prow[m0] = (unsigned short)pos;
         acc |= (unsigned long long)(b & ((1u << n) - 1u)) << nacc;
         nacc += n;
         if (nacc >= 32) { if (nwords < cap_words) bits[nwords] = (unsigned)acc; nwords++; acc >>= 32; nacc -= 32; }
     }
-    if (const int rem = n3 - 9 * periods) {
+    const int rem = n3 - 9 * periods;
+    if (rem) {
         const unsigned w = wrow[periods];
         int n;
-        const unsigned b = nvx_fsm_partial_period(w, rem, &r, &n);
+        unsigned pos;
+        const unsigned b = nvx_fsm_partial_period_pos(w, rem, &r, &n, &pos);
+        if (SOFT) prow[periods] = (unsigned short)pos;   // (periods < y3_cap / 9: a ragged launch is shorter than its frames)
         acc |= (unsigned long long)(b & ((1u << n) - 1u)) << nacc;
         nacc += n;
         if (nacc >= 32) { if (nwords < cap_words) bits[nwords] = (unsigned)acc; nwords++; acc >>= 32; nacc -= 32; }
@@ -526,6 +567,54 @@ __global__ __launch_bounds__(64) void nvx_demod_fsm(nvx_demod_args a)
     SI(DI_SYNCED) = synced; SI(DI_SYNC_OFF) = synced ? r.so : 0; SI(DI_NEXT_SYNC_OFF) = r.nso;
     SI(DI_PHASE) = r.phase1 - 1; SI(DI_PREV_OFFSET) = r.prev_offset;
 #undef SI
+    if (SOFT) {
+        // ---- second pass: the noted windows, in bit order.  Every t is a sample of this launch (a whole period's k <= 8, the
+        // ragged period's k < rem), so y3[t - 4 .. t] lies in the chain's row or, for t < 4, in the carried history
+        const double2 *y3 = a.y3 + (size_t)slot * a.y3_cap + a.y3_base;
+        const double *hist = (parity ? a.dstate[1] : a.dstate[0]) + (size_t)slot * NVX_DEMOD_DOUBLES + DS_Y3;
+        float *row = a.soft + (size_t)slot * a.soft_cap;
+        const int cap = a.soft_cap;
+        const int whole = periods & ~7;                  // the periods noted eight to a store
+        int j = 0, m = 0;
+        const uint4 *notes = (const uint4 *)prow;        // (read as they were stored: eight to a uint4, the rest one by one)
+        if (whole) {                                     // the first eight periods: only these can reach the history
+            const uint4 pv = notes[0];
+            const unsigned pcur[8] = { pv.x & 0xffffu, pv.x >> 16, pv.y & 0xffffu, pv.y >> 16,
+                                       pv.z & 0xffffu, pv.z >> 16, pv.w & 0xffffu, pv.w >> 16 };
+#pragma unroll
+            for (int i = 0; i < 8; i++) j = fsm_soft_period(y3, hist, i, pcur[i], row, cap, j);
+            m = 8;
+        }
+        uint4 pnext = whole > 8 ? notes[1] : uint4{ 0, 0, 0, 0 };
+        for (; m < whole; m += 8) {
+            const uint4 pv = pnext;
+            if (m + 16 <= whole) pnext = notes[m / 8 + 1];
+            const unsigned pcur[8] = { pv.x & 0xffffu, pv.x >> 16, pv.y & 0xffffu, pv.y >> 16,
+                                       pv.z & 0xffffu, pv.z >> 16, pv.w & 0xffffu, pv.w >> 16 };
+            // a period's first decision, evaluated whether it exists or not (none: the window ending on the period's last
+            // sample, dropped below): NVX_SOFT_INFLIGHT independent windows in flight.  Two: 106 VGPRs, and the step with soft
+            // values on is 0.1 ms shorter than with one (85); eight would take 232, more than the next launch's cascade grid
+            // leaves free on a SIMD -- the kernel's waves, soft or not, would wait for it (profiles/TUNING.md)
+#pragma unroll
+            for (int i = 0; i < 8; i += NVX_SOFT_INFLIGHT) {
+                float v[NVX_SOFT_INFLIGHT];
+#pragma unroll
+                for (int u = 0; u < NVX_SOFT_INFLIGHT; u++)
+                    v[u] = fsm_soft_at<false>(y3, hist, 9 * (m + i + u) + (NVX_FSM_POS_N(pcur[i + u]) ? NVX_FSM_POS_K1(pcur[i + u]) : 8));
+#pragma unroll
+                for (int u = 0; u < NVX_SOFT_INFLIGHT; u++) {
+                    const int n = NVX_FSM_POS_N(pcur[i + u]);
+                    if (n >= 1) { if (j < cap) row[j] = v[u]; j++; }
+                    if (n == 2) {                        // (the timing slewed forward: rare)
+                        const float v2 = fsm_soft_at<false>(y3, hist, 9 * (m + i + u) + NVX_FSM_POS_K2(pcur[i + u]));
+                        if (j < cap) row[j] = v2;
+                        j++;
+                    }
+                }
+            }
+        }
+        for (; m < periods + (rem ? 1 : 0); m++) j = fsm_soft_period(y3, hist, m, prow[m], row, cap, j);
+    }
     if (a.sig) {                                         // the signal report: the front's partials of the chain, in tile order
         const nvx_sig_rec *p = a.sig_part + (size_t)slot * a.sig_stride;
         nvx_sig_rec s = p[0];
@@ -537,6 +626,19 @@ __global__ __launch_bounds__(64) void nvx_demod_fsm(nvx_demod_args a)
         }
         a.sig[slot] = s;
     }
+}
+
+__global__ __launch_bounds__(64) void nvx_demod_fsm(nvx_demod_args a)
+{
+    __shared__ uint32_t s_tab[NVX_FSM_TABLE_ALLOC];
+    {
+        const uint4 *src = (const uint4 *)a.fsm_table;
+        uint4 *dst = (uint4 *)s_tab;
+        for (int i = threadIdx.x; i < NVX_FSM_TABLE_ALLOC / 4; i += 64) dst[i] = src[i];
+    }
+    __syncthreads();
+    if (a.soft) fsm_chain<true>(a, s_tab);
+    else fsm_chain<false>(a, s_tab);
 }
 
 // Which form of the front a launch takes: the number of tile workgroups per chain (the tile-parallel form), or 0 (the walk)

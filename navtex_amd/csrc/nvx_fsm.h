@@ -112,10 +112,17 @@ typedef struct nvx_fsm_regs {
     int prev_offset;     /* slew limiter state, -1 before the first decision           */
 } nvx_fsm_regs;
 
+/* What a bit period decided, for whoever wants the decided bits' windows afterwards (the soft values, nvx_demod.hip):
+ * bits 0-1 the number of decisions, 2-5 / 6-9 the samples k of the period their windows end on. */
+#define NVX_FSM_POS(n, k1, k2) ((unsigned)(n) | ((unsigned)(k1) << 2) | ((unsigned)(k2) << 6))
+#define NVX_FSM_POS_N(p)  ((int)((p) & 3u))
+#define NVX_FSM_POS_K1(p) ((int)(((p) >> 2) & 15u))
+#define NVX_FSM_POS_K2(p) ((int)(((p) >> 6) & 15u))
+
 /* One bit period.  w = the front kernel's word: bits 0..8 the mark/space decision if a window
  * ended on sample k ('B' = 1), bits 12..15 the arg-max of the timing evaluation (15 = none).
- * Returns the decided bits in the low *n_out (0..2) positions, first decision lowest.       */
-NVX_FSM_HD unsigned nvx_fsm_period(const uint32_t *tab, unsigned w, nvx_fsm_regs *r, int *n_out)
+ * Returns the decided bits in the low *n_out (0..2) positions, first decision lowest; *pos_out: NVX_FSM_POS of the period. */
+NVX_FSM_HD unsigned nvx_fsm_period_pos(const uint32_t *tab, unsigned w, nvx_fsm_regs *r, int *n_out, unsigned *pos_out)
 {
     const unsigned raw = w >> 12;
     const uint32_t t = tab[NVX_FSM_TIMING_BASE + (r->prev_offset + 1) * 10 + (int)(raw > 9u ? 9u : raw)];
@@ -129,17 +136,24 @@ NVX_FSM_HD unsigned nvx_fsm_period(const uint32_t *tab, unsigned w, nvx_fsm_regs
     r->so = live ? NVX_FSM_E_SO(e) : r->so;
     r->nso = nso_new;
     *n_out = live ? NVX_FSM_E_N(e) : 0;
+    *pos_out = live ? (unsigned)((e >> 8) & 0x3ffu) : 0u;        /* the entry's bits 8-17 are NVX_FSM_POS(n, k1, k2) */
     return ((w >> NVX_FSM_E_K1(e)) & 1u) | (((w >> NVX_FSM_E_K2(e)) & 1u) << 1);
+}
+NVX_FSM_HD unsigned nvx_fsm_period(const uint32_t *tab, unsigned w, nvx_fsm_regs *r, int *n_out)
+{
+    unsigned pos;
+    return nvx_fsm_period_pos(tab, w, r, n_out, &pos);
 }
 
 /* The first `rem` (1..8) samples of a bit period -- the period in which a stream's input ends: the per-sample rule
  * itself, sample by sample (the reference's decoder stops with its last sample, receiver/capt_sched.c:509-513).  w as
- * above; its timing arg-max is only looked at when the period's sample 6 exists.  Returns the decided bits, *n_out of them. */
-NVX_FSM_HD unsigned nvx_fsm_partial_period(unsigned w, int rem, nvx_fsm_regs *r, int *n_out)
+ * above; its timing arg-max is only looked at when the period's sample 6 exists.  Returns the decided bits, *n_out of them;
+ * *pos_out as above. */
+NVX_FSM_HD unsigned nvx_fsm_partial_period_pos(unsigned w, int rem, nvx_fsm_regs *r, int *n_out, unsigned *pos_out)
 {
     int synced = r->so != NVX_FSM_UNSYNCED;
     int phase = r->phase1 - 1, sync_off = synced ? r->so : 0, next_sync_off = r->nso, prev_offset = r->prev_offset;
-    unsigned bits = 0;
+    unsigned bits = 0, kk = 0;
     int n = 0;
     for (int k = 0; k < rem; k++) {
         if (k == NVX_FSM_TIMING_SAMPLE) {
@@ -150,11 +164,17 @@ NVX_FSM_HD unsigned nvx_fsm_partial_period(unsigned w, int rem, nvx_fsm_regs *r,
                 synced = 1;
             }
         }
-        if (nvx_fsm_bit_step(k, synced, &phase, &sync_off, next_sync_off)) { bits |= ((w >> k) & 1u) << n; n++; }
+        if (nvx_fsm_bit_step(k, synced, &phase, &sync_off, next_sync_off)) { bits |= ((w >> k) & 1u) << n; kk |= (unsigned)k << (4 * n); n++; }
     }
     r->phase1 = phase + 1; r->so = synced ? sync_off : NVX_FSM_UNSYNCED; r->nso = next_sync_off; r->prev_offset = prev_offset;
     *n_out = n;
+    *pos_out = NVX_FSM_POS(n, kk & 15u, (kk >> 4) & 15u);
     return bits;
+}
+NVX_FSM_HD unsigned nvx_fsm_partial_period(unsigned w, int rem, nvx_fsm_regs *r, int *n_out)
+{
+    unsigned pos;
+    return nvx_fsm_partial_period_pos(w, rem, r, n_out, &pos);
 }
 
 #endif

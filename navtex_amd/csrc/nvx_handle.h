@@ -59,6 +59,13 @@ struct Slot {                          // one (stream, chain)
     nvx_sitor *sitor = nullptr;
     std::vector<Message> outbox;       // messages completed during a (possibly threaded) collect
     SigSums sig;                       // signal report over the collected launches (while reports are on)
+    // soft decoding (navtex_amd_soft.h): the second character layer and its messages; the values kept for nvx_poll_soft
+    // (NVX_SOFT_KEEP), trimmed as bits is, with their own cursor; values taken in since create / reset / the mode went on
+    nvx_sitor *soft_sitor = nullptr;
+    std::vector<Message> soft_outbox;
+    std::vector<float> soft;
+    size_t soft_base = 0, soft_polled = 0;
+    uint64_t soft_count = 0;
 };
 
 struct Result {                        // one in-flight launch's bit output
@@ -78,6 +85,10 @@ struct Result {                        // one in-flight launch's bit output
     // signal reports (nvx_enable_signal_report): the launch's record per slot, device and pinned; sig = the launch carried them
     nvx_sig_rec *d_sig = nullptr, *h_sig = nullptr;
     bool sig = false;
+    // soft decoding (nvx_enable_soft): the launch's soft values [n_slots][soft_cap], device and pinned; soft = the launch carried them
+    float *d_soft = nullptr, *h_soft = nullptr;
+    bool soft = false;
+    int soft_pitch = 0;                // values per slot in this launch's rows (as long as its bits can reach, at most soft_cap)
 };
 
 // Decode latency of the live path (r4).  The reference decodes synchronously, sample by sample, and calls add_message
@@ -158,6 +169,12 @@ struct nvx_handle {
     bool sig_on = false;
     nvx_sig_rec *d_sig_part = nullptr;
     int sig_stride = 0;
+    // nvx_enable_soft's buffers and state, made and freed there (and by free_handle): Result::d_soft / h_soft, the FSM
+    // kernel's notes [n_slots][y3_cap / 9], the slots' soft character layers; where their messages go (kept while off)
+    int soft_mode = 0;
+    int soft_cap = 0;                  // values per slot the buffers hold: as many as a launch of max_frames can yield bits
+    unsigned short *d_soft_pos = nullptr;
+    nvx_message_fn soft_fn = nullptr; void *soft_user = nullptr;
     // carrier tuning (navtex_amd_tune.h): k per slot, and its device copy behind the chain masks (NVX_TUNE_K_OFFSET)
     std::vector<int> tune_k;
     int *d_tune_k = nullptr;
@@ -193,8 +210,8 @@ struct nvx_handle {
     int last_n3 = 0;
     // timing
     bool timing = false;
-    float ms[3] = { 0.f, 0.f, 0.f };     // last collected launch: cascade, demodulator (front + FSM), nvx_fir3
-    double ms_sum[3] = { 0.0, 0.0, 0.0 };   // over all collected launches since the last stats reset
+    float ms[4] = { 0.f, 0.f, 0.f, 0.f };   // last collected launch: cascade, demodulator (front + FSM), nvx_fir3, the FSM kernel alone
+    double ms_sum[4] = { 0.0, 0.0, 0.0, 0.0 };   // over all collected launches since the last stats reset
     uint64_t ms_count = 0;
     // host
     std::vector<uint8_t> masks;
@@ -232,7 +249,7 @@ struct nvx_handle {
     std::condition_variable wr_cv;
 };
 
-struct SinkCtx { nvx_handle *h; int stream; int slot; };
+struct SinkCtx { nvx_handle *h; int stream; int slot; bool soft = false; };     // soft: the slot's soft character layer
 
 // Scope in which the staging sets may be rearranged: raised with the handle locked, waits (lock released meanwhile)
 // until the unlocked copies in flight have been committed; pushes start no new unlocked copy while one is up.

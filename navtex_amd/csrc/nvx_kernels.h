@@ -186,6 +186,12 @@ typedef struct {
     nvx_sig_rec *sig_part;     /* [n_slots][sig_stride] partial records of the front's workgroups, in tile order          */
     int sig_stride;            /* partials per slot the buffer holds (the launcher refuses a launch that needs more)       */
     int sig_parts;             /* set by the launchers: partials per slot this launch writes (1 = the walk)                */
+    /* soft decisions (navtex_amd_soft.h): per decided bit Brot - Yrot of its window, float32, in bit order beside the bits */
+    float *soft;               /* soft values on: [n_slots][soft_cap], written by nvx_demod_fsm; NULL = off                */
+    int soft_cap;              /* values per slot this launch's rows hold (a launch yields as many as bits; what does not  */
+                               /* fit is not stored)                                                                       */
+    unsigned short *soft_pos;  /* [n_slots][y3_cap/9] nvx_demod_fsm's own notes: per bit period NVX_FSM_POS (nvx_fsm.h),    */
+                               /* the samples its decisions fell on (rows 16-byte aligned, as words)                       */
 } nvx_demod_args;
 
 typedef struct {

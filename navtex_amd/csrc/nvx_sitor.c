@@ -17,8 +17,15 @@
  * signals in a row in the DX slot end the emission; more than 12 bad codes in
  * the last 20 abort; bbbb keeps the FIRST id seen until the message closes;
  * code 0x5C decodes to ' ' and 0x19 to '-' in both shifts.
+ *
+ * Soft mode (navtex_amd_soft.h, not in the reference): every bit comes with a
+ * metric (> 0 = 'B'); the character printed in the RX slot is decided from the
+ * metrics of the RX code and of its DX twin together (soft_code below).
+ * Everything that is control -- phasing detector, slot tracking, end of
+ * emission, error window, mute -- stays on the hard bits.
  */
 #include "navtex_amd.h"
+#include "navtex_amd_soft.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -55,6 +62,9 @@ struct nvx_sitor {
     /* character level */
     int slot, figures;
     unsigned char dx[3]; int dx_pos, dx_full;
+    /* soft mode: the metrics of the code being collected and of the last three DX codes (beside dx[]), first-received bit first */
+    int soft;
+    double cur[7], dxm[3][7];
     int idle_run, prev_dx_idle;
     char errwin[NVX_ERRWIN]; int err_pos, err_full, err_count;
     /* message level */
@@ -190,6 +200,29 @@ static void emit_code(nvx_sitor *s, unsigned code)         /* nav_b_sm.C:100-145
     } }
 }
 
+/* Soft mode: the code printed for an RX code and its DX twin, from their metrics (rx[i], dx[i]: bit i as received, MSB of
+ * the code first; > 0 = 'B' = code bit 0).  Data hypothesis: both slots carry one 4B/3Y code; the best of the 35 under
+ * the summed metrics m = rx + dx has 'Y' on the three smallest m (ties: the earlier bit), score sd = sum m - 2 * (those
+ * three).  Phasing hypothesis: the slots legitimately differ, RX = alpha, DX = beta; score sp = correlation of each
+ * slot with its own code.  sp > sd (strictly): alpha, which prints nothing.  All sums in double, in bit order. */
+static unsigned soft_code(const double *rx, const double *dx)
+{
+    double m[7], total = 0.0, three = 0.0, sp_rx = 0.0, sp_dx = 0.0;
+    unsigned code = 0;
+    for (int i = 0; i < 7; i++) { m[i] = rx[i] + dx[i]; total += m[i]; }
+    for (int k = 0; k < 3; k++) {
+        int best = -1;
+        for (int i = 0; i < 7; i++)
+            if (!((code >> (6 - i)) & 1) && (best < 0 || m[i] < m[best])) best = i;
+        code |= 1u << (6 - best);
+    }
+    for (int i = 0; i < 7; i++) if ((code >> (6 - i)) & 1) three += m[i];
+    const double sd = total - 2.0 * three;
+    for (int i = 0; i < 7; i++) sp_rx += ((NVX_ALPHA >> (6 - i)) & 1) ? -rx[i] : rx[i];
+    for (int i = 0; i < 7; i++) sp_dx += ((NVX_BETA >> (6 - i)) & 1) ? -dx[i] : dx[i];
+    return (sp_rx + sp_dx > sd) ? NVX_ALPHA : code;
+}
+
 static void receive_code(nvx_sitor *s, unsigned code)      /* nav_b_sm.C:150-262 */
 {
     switch (s->slot) {
@@ -199,6 +232,7 @@ static void receive_code(nvx_sitor *s, unsigned code)      /* nav_b_sm.C:150-262
         break;
     case SLOT_EXPECT_DX:                                   /* S_BYTE_RECEIVED_RX */
         s->dx[s->dx_pos] = (unsigned char)code;
+        if (s->soft) memcpy(s->dxm[s->dx_pos], s->cur, sizeof s->cur);
         if (++s->dx_pos == 3) { s->dx_pos = 0; s->dx_full = 1; }
         if (code == NVX_ALPHA) {
             trace(s, "\n alpha received in DX position\n");
@@ -217,7 +251,8 @@ static void receive_code(nvx_sitor *s, unsigned code)      /* nav_b_sm.C:150-262
     case SLOT_EXPECT_RX:                                   /* S_BYTE_RECEIVED_DX */
         if (s->dx_full) {
             unsigned twin = s->dx[s->dx_pos];              /* the DX copy sent two pairs earlier */
-            if (nvx_ltrs[code] != '_')      emit_code(s, code);
+            if (s->soft)                    emit_code(s, soft_code(s->cur, s->dxm[s->dx_pos]));
+            else if (nvx_ltrs[code] != '_') emit_code(s, code);
             else if (nvx_ltrs[twin] != '_') emit_code(s, twin);
             else                            emit_code(s, 0);
         }
@@ -237,10 +272,11 @@ static void receive_code(nvx_sitor *s, unsigned code)      /* nav_b_sm.C:150-262
     }
 }
 
-void nvx_sitor_receive_bit(nvx_sitor *s, char bit)         /* nav_b_sm.C:266-634 */
+/* one bit and its metric (soft mode reads it; the sign is the caller's business) */
+static void receive_bit_metric(nvx_sitor *s, char bit, double metric)         /* nav_b_sm.C:266-634 */
 {
-    if (!s) return;
     if (s->enabled) {
+        s->cur[s->nbits] = metric;                         /* (nbits < 7 here) */
         /* the reference shifts a signed char; only 7 bits are ever collected
          * between two clears, so an unsigned accumulator is equivalent        */
         s->acc = ((s->acc << 1) | (bit == 'Y')) & 0xff;
@@ -268,11 +304,25 @@ void nvx_sitor_receive_bit(nvx_sitor *s, char bit)         /* nav_b_sm.C:266-634
     }
 }
 
+void nvx_sitor_receive_bit(nvx_sitor *s, char bit)
+{
+    if (!s) return;
+    receive_bit_metric(s, bit, bit == 'B' ? 1.0 : -1.0);  /* a hard bit in soft mode: unit weight */
+}
+
 void nvx_sitor_receive_bits(nvx_sitor *s, const char *bits, size_t n)
 {
     if (!s || !bits) return;
     for (size_t i = 0; i < n; i++)
         if (bits[i] == 'B' || bits[i] == 'Y') nvx_sitor_receive_bit(s, bits[i]);
+}
+
+void nvx_sitor_set_soft(nvx_sitor *s, int on) { if (s) s->soft = on != 0; }
+
+void nvx_sitor_receive_soft(nvx_sitor *s, const float *soft, size_t n)
+{
+    if (!s || !soft) return;
+    for (size_t i = 0; i < n; i++) receive_bit_metric(s, soft[i] > 0.0f ? 'B' : 'Y', (double)soft[i]);
 }
 
 /* ========================================================================== */
