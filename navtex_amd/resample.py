@@ -48,6 +48,7 @@ def _load() -> C.CDLL:
         "nvx_resample_timing": (i, [vp, i]),
         "nvx_resample_time_stats": (i, [vp, C.POINTER(C.c_double), C.POINTER(u64), i]),
         "nvx_resample_last_error": (C.c_char_p, []),
+        "nvx_resample_debug_last_launch": (C.c_int64, [vp, ip, ip, ip, ip, ip, C.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -140,6 +141,14 @@ class Resampler:
         s, n = C.c_double(), C.c_uint64()
         _check(lib.nvx_resample_time_stats(self._h, C.byref(s), C.byref(n), int(reset)), "nvx_resample_time_stats")
         return s.value, n.value
+
+    def debug_last_launch(self) -> dict:
+        """For tests (nvx_resample_debug_last_launch): the shape of the last kernel launch as the host handed it over."""
+        K, tiles, tpc, chunks, in_lds, lds = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+        n = _check(lib.nvx_resample_debug_last_launch(self._h, C.byref(K), C.byref(tiles), C.byref(tpc), C.byref(chunks), C.byref(in_lds),
+                                                      C.byref(lds)), "nvx_resample_debug_last_launch")
+        return {"launches": n, "K": K.value, "tiles": tiles.value, "tiles_per_chunk": tpc.value, "chunks": chunks.value,
+                "taps_in_lds": bool(in_lds.value), "lds_bytes": lds.value}
 
     def close(self) -> None:
         if getattr(self, "_h", None):

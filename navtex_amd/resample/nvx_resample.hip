@@ -247,10 +247,15 @@ hipError_t nvx_rs_prepare(void)
     return hipSuccess;
 }
 
+size_t nvx_rs_lds_bytes(const nvx_rs_args *a, bool taps_in_lds)
+{
+    return (size_t)NVX_RS_PLANE * 4 + (taps_in_lds ? (size_t)a->tap_dw * 4 : 0);
+}
+
 hipError_t nvx_rs_launch(const nvx_rs_args *a, int format, int n_streams, int chunks, bool taps_in_lds, hipStream_t s)
 {
     const dim3 grid((unsigned)chunks, (unsigned)n_streams);
-    const size_t lds_bytes = (size_t)NVX_RS_PLANE * 4 + (taps_in_lds ? (size_t)a->tap_dw * 4 : 0);
+    const size_t lds_bytes = nvx_rs_lds_bytes(a, taps_in_lds);
     if (lds_bytes > LDS_MAX) return hipErrorInvalidValue;
     switch (format * 2 + (taps_in_lds ? 1 : 0)) {
     case NVX_RS_CS16 * 2 + 1: return launch<NVX_RS_CS16, true>(a, grid, lds_bytes, s);

@@ -56,6 +56,8 @@ struct nvx_resampler {
     double sum_ms = 0.0; uint64_t launches = 0;
     void *d_push_in = nullptr; uint32_t *d_push_out = nullptr;     // nvx_resample_push's staging, grown on demand
     size_t push_in_cap = 0, push_out_cap = 0;
+    struct { int K, tiles, tiles_per_chunk, chunks, taps_in_lds; size_t lds_bytes; } last = {};      // nvx_resample_debug_last_launch
+    int64_t kernel_launches = 0;
 };
 
 static bool valid(const nvx_resampler *r, const char *what)
@@ -276,6 +278,22 @@ extern "C" int nvx_resample_time_stats(nvx_resampler *r, double *sum_ms, uint64_
     return NVX_OK;
 }
 
+extern "C" int64_t nvx_resample_debug_last_launch(nvx_resampler *r, int *K, int *tiles, int *tiles_per_chunk, int *chunks,
+                                                  int *taps_in_lds, size_t *lds_bytes)
+{
+    if (!valid(r, "nvx_resample_debug_last_launch")) return NVX_ERR_ARG;
+    std::lock_guard<std::mutex> lk(r->mu);
+    if (r->kernel_launches) {
+        if (K) *K = r->last.K;
+        if (tiles) *tiles = r->last.tiles;
+        if (tiles_per_chunk) *tiles_per_chunk = r->last.tiles_per_chunk;
+        if (chunks) *chunks = r->last.chunks;
+        if (taps_in_lds) *taps_in_lds = r->last.taps_in_lds;
+        if (lds_bytes) *lds_bytes = r->last.lds_bytes;
+    }
+    return r->kernel_launches;
+}
+
 // ------------------------------------------------------------------------------------------------------------ launches
 // One launch over streams [first_stream, first_stream + n_streams) of the plan, which stand at `consumed` and read history
 // row `parity`; the caller holds r->mu and has checked every span.
@@ -322,6 +340,8 @@ static int launch(nvx_resampler *r, int first_stream, int n_streams, uint64_t co
         HIP_TRY(hipEventRecord(ev.first, s));
     }
     HIP_TRY(nvx_rs_launch(&a, r->format, n_streams, chunks, r->taps_in_lds, s));
+    r->last = { a.K, a.tiles, a.tiles_per_chunk, chunks, r->taps_in_lds ? 1 : 0, nvx_rs_lds_bytes(&a, r->taps_in_lds) };
+    r->kernel_launches++;
     if (timed) { HIP_TRY(hipEventRecord(ev.second, s)); r->pending.push_back(ev); }
     return NVX_OK;
 }

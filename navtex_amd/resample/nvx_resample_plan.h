@@ -26,6 +26,13 @@ int nvx_rs_plan_numbers(uint32_t fi, int *L, int *M, int *T, const char **why);
 int nvx_rs_plan_taps(uint32_t fi, int L, int T, int16_t *taps, const char **why);
 uint64_t nvx_rs_outputs_after(uint64_t n, int L, int M);
 
+/* For tests: the shape of the handle's last kernel launch, from the values handed to nvx_rs_launch -- outputs per thread
+ * and tile, tiles per stream, tiles per workgroup, workgroups per stream, whether the tap table went to the LDS, and the
+ * dynamic LDS bytes of the launch.  Returns the launches made since creation (0: nothing was written); any pointer may be
+ * NULL. */
+NVX_API int64_t nvx_resample_debug_last_launch(nvx_resampler *r, int *K, int *tiles, int *tiles_per_chunk, int *chunks,
+                                               int *taps_in_lds, size_t *lds_bytes);
+
 #ifdef __cplusplus
 }
 
@@ -58,6 +65,7 @@ struct nvx_rs_args {
 #include <hip/hip_runtime.h>
 /* grid (chunks, n_streams); taps_in_lds: the table fits NVX_RS_TAPS_LDS_MAX */
 hipError_t nvx_rs_launch(const nvx_rs_args *a, int format, int n_streams, int chunks, bool taps_in_lds, hipStream_t s);
+size_t nvx_rs_lds_bytes(const nvx_rs_args *a, bool taps_in_lds);      /* the dynamic LDS of that launch */
 hipError_t nvx_rs_prepare(void);            /* once per process: the kernels' LDS limit */
 #endif
 

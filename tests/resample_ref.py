@@ -75,6 +75,31 @@ def resample_all(samples: np.ndarray, fmt: int, taps: np.ndarray, L: int, M: int
     return np.concatenate(parts) if parts else np.zeros((0, 2), dtype=np.int16)
 
 
+def resample_streams(x: np.ndarray, taps: np.ndarray, L: int, M: int, out_block: int = 32) -> np.ndarray:
+    """resample() from a reset for many streams of one length at once: x [streams, n, 2] int64 (converted) -> int16
+    [streams, n_out, 2].  All streams share (q, r), so a block of outputs is one matrix product of the streams' samples with
+    the block's taps laid out by input index.  The products run in float64 and are exact: every term is below 2^31 and every
+    partial sum of the at most T terms of an output below 2^53, so the words equal resample()'s."""
+    x = np.asarray(x, dtype=np.int64)
+    ns, n, T = x.shape[0], x.shape[1], taps.shape[1]
+    ext = np.zeros((ns, 2, n + T - 1), dtype=np.float64)                       # ext[.., k + T - 1] = sample k; silence in front
+    ext[:, :, T - 1:] = x.transpose(0, 2, 1)
+    n_out = outputs_after(n, L, M)
+    out = np.empty((ns, n_out, 2), dtype=np.int16)
+    for o in range(0, n_out, out_block):
+        idx = np.arange(o, min(n_out, o + out_block), dtype=np.int64)
+        q, r = idx * M // L, idx * M % L
+        lo, hi = int(q[0]), int(q[-1]) + T                                     # ext[lo .. hi): samples q[0] - (T-1) .. q[-1]
+        w = np.zeros((hi - lo, len(idx)), dtype=np.float64)
+        for t in range(T):
+            w[q - t + T - 1 - lo, np.arange(len(idx))] = taps[r, t]
+        acc = ext[:, :, lo:hi] @ w                                             # [streams, 2, outputs]
+        assert np.abs(acc).max() + (1 << (S - 1)) < 2 ** 31, "the accumulator left int32"
+        y = np.clip((acc.astype(np.int64) + (1 << (S - 1))) >> S, -32768, 32767).astype(np.int16)
+        out[:, idx, :] = y.transpose(0, 2, 1)
+    return out
+
+
 def response_db(taps: np.ndarray, L: int, fi: int, freqs_hz: np.ndarray) -> np.ndarray:
     """|H(f)| / |H(0)| in dB of the prototype p[r + t L] = taps[r, t] at rate L fi."""
     p = taps.astype(np.float64).T.reshape(-1)                                  # [t, r] flattened: index t L + r

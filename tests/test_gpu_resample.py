@@ -71,7 +71,9 @@ def _inputs(nv, fi, fmt, n, seed):
 
 def _run_resident(nv, r, rows, chunks, pitch_extra=0, out_first=0, sentinel=0x5a5a1234):
     """The rows ([n, 2] each, all of one length) through nvx_resample_resident in calls of `chunks` samples; every call's
-    input is uploaded to the start of the input rows (rows are 16-byte aligned).  Returns int16 [streams, n_out, 2]."""
+    input is uploaded to the start of the input rows (rows are 16-byte aligned) as whole rows: behind a call's n_in samples
+    the row is full scale up to the pitch (with pitch_extra = 0 that is the rounding to 8 alone), so a read behind n_in
+    changes the output.  Returns int16 [streams, n_out, 2]."""
     ns, n = len(rows), len(rows[0])
     assert sum(chunks) == n and ns == r.n_streams
     bps = rows[0].dtype.itemsize * 2
@@ -82,11 +84,14 @@ def _run_resident(nv, r, rows, chunks, pitch_extra=0, out_first=0, sentinel=0x5a
     d_in = nv.DeviceBuffer(ns * pitch_in * bps)
     d_out = nv.DeviceBuffer(ns * pitch_out * 4)
     d_out.upload(np.full(ns * pitch_out, sentinel, dtype=np.uint32))
+    dt = rows[0].dtype
+    block = np.empty((ns, pitch_in, 2), dtype=dt)
     pos = made = 0
     for c in chunks:
-        if c:
-            for s in range(ns):
-                d_in.upload(rows[s][pos:pos + c], s * pitch_in * bps)
+        block[:, c:] = 1.0 if dt == np.float32 else np.iinfo(dt).max
+        for s in range(ns):
+            block[s, :c] = rows[s][pos:pos + c]
+        d_in.upload(block)
         got = r.resident(d_in, pitch_in, c, d_out, pitch_out, out_first + made)
         assert got == rr.outputs_after(start + pos + c, r.L, r.M) - rr.outputs_after(start + pos, r.L, r.M)
         pos, made = pos + c, made + got
@@ -230,6 +235,14 @@ def test_span_errors_launch_nothing(nv, rs):
             assert call(*args) == ARG, name
             assert rs.lib.nvx_resample_last_error() != b""
         assert r.time_stats() == (0.0, 0) and r.position(0) == (0, 0) and r.position(1) == (0, 0)
+        # more outputs than an int holds: 2^30 samples at 96 kS/s are 2.8e9 outputs
+        with rs.Resampler(96000, rr.CS16) as up:
+            up.timing(True)
+            assert rs.out_count(96000, 0, 2 ** 30) == 2 ** 30 * 21 // 8 > 2 ** 31 - 1
+            k.value = 99
+            assert rs.lib.nvx_resample_resident(up._h, d_in.ptr, 2 ** 30, 2 ** 30, d_out.ptr, 2 ** 32, 0, C.byref(k), None) == ARG, "too many outputs"
+            assert rs.lib.nvx_resample_last_error() != b"" and k.value == 99
+            assert up.time_stats() == (0.0, 0) and up.debug_last_launch()["launches"] == 0 and up.position(0) == (0, 0)
         assert call(d_in.ptr, n, 0, d_out.ptr, outs, 0) == 0 and k.value == 0 and r.time_stats()[1] == 0       # nothing to do: no launch
         assert call(d_in.ptr, n, n, d_out.ptr, outs, 0) == 0 and k.value == outs
         ms, launches = r.time_stats()

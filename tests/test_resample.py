@@ -65,7 +65,9 @@ def test_the_companion_links_neither_the_product_library_nor_test_infrastructure
     # it defines nothing but its own interface, and needs no nvx_ symbol from elsewhere
     nm = subprocess.run(["nm", "-D", str(lib)], capture_output=True, text=True, check=True).stdout
     defined = sorted(l.split()[-1] for l in nm.splitlines() if " T " in l and "nvx_" in l)
-    assert defined == SYMBOLS
+    hook = "nvx_resample_debug_last_launch"              # the tests' one hook: declared in nvx_resample_plan.h, not in the public header
+    assert defined == sorted(SYMBOLS + [hook]) and hook not in HEADER.read_text()
+    assert hook in (ROOT / "navtex_amd" / "resample" / "nvx_resample_plan.h").read_text() and rs.lib.nvx_resample_debug_last_launch(None, *[None] * 6) < 0
     assert not [l for l in nm.splitlines() if " U " in l and "nvx" in l]
     for path in (ROOT / "navtex_amd" / "resample").iterdir():
         text = path.read_text()
