@@ -407,6 +407,18 @@ NVX_API int   nvx_fsm_selftest(uint32_t seed, int periods);
  * through three frames (the priming thresholds of the timing filter are the one thing that is not periodic): NVX_ERR_STATE. */
 #define NVX_CLOCK_PERIOD 163296
 NVX_API int   nvx_debug_advance_clock(nvx_handle *h, int stream, uint64_t periods);
+/* Force the form of the kernels this handle launches (tests, A/B runs; a receiver never needs it: the automatic
+ * choice is the measured optimum).  Each value: -1 = automatic, 0 / 1 = forced off / on.
+ *   independent      cascade and fused wideband kernels: units rebuild their histories (pre-roll) instead of handing over
+ *   dynamic_preroll  cascade hand-over launches: a unit whose predecessor still runs pre-rolls (1, the default) or waits (0)
+ *   demod_tiles      demodulator front: tile-parallel form (taken only where a launch has >= 3 tiles) or the walk
+ * Applies to launches enqueued after the call; launches in flight keep theirs.  All forms are bit-identical and carry the
+ * same state, so the form may change from launch to launch.  Configuration: survives nvx_reset / nvx_stream_reset.   */
+NVX_API int   nvx_debug_set_forms(nvx_handle *h, int independent, int dynamic_preroll, int demod_tiles);
+/* The forms the handle's most recently ENQUEUED launch took, as the launchers resolved them: independent 0/1,
+ * dynamic_preroll 0/1 (-1: wideband handle), front_tile_wgs = tile workgroups per chain (0 = the walk).
+ * NVX_ERR_STATE before the first launch.  Any out pointer may be NULL.                                              */
+NVX_API int   nvx_debug_last_forms(nvx_handle *h, int *independent, int *dynamic_preroll, int *front_tile_wgs);
 /* allocate (1) / release (0) the demodulator's debug buffers: delta-phi for nvx_debug_dphi, and the bit-timing taps */
 NVX_API int   nvx_enable_debug(nvx_handle *h, int enabled);
 /* test / diagnostics hook: the carried FIR state block of one decoded stream -- the block the stream's NEXT launch will

@@ -8,6 +8,7 @@ signal processing and no fallback path.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -236,6 +237,25 @@ class HandleStats:
         N.check(lib.nvx_get_carrier(self._h, stream, chain, C.byref(off), C.byref(ref)), "nvx_get_carrier")
         return off.value, bool(ref.value)
 
+    def set_forms(self, independent: int = -1, dynamic_preroll: int = -1, demod_tiles: int = -1) -> None:
+        """Force the kernel forms of the launches from here on (nvx_debug_set_forms): each -1 = automatic, 0 / 1 = off / on."""
+        N.check(lib.nvx_debug_set_forms(self._h, independent, dynamic_preroll, demod_tiles), "nvx_debug_set_forms")
+
+    def last_forms(self) -> Tuple[int, int, int]:
+        """(independent, dynamic_preroll, front_tile_wgs) the most recently enqueued launch took (nvx_debug_last_forms)."""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        N.check(lib.nvx_debug_last_forms(self._h, C.byref(a), C.byref(b), C.byref(c)), "nvx_debug_last_forms")
+        return a.value, b.value, c.value
+
+    def _apply_forms(self, forms: Optional[Sequence[int]]) -> None:
+        """What the constructors do with forms=: given, it is set; None takes NVX_INDEPENDENT, NVX_DYNAMIC_PREROLL and
+        NVX_DEMOD_TILES from the environment (this binding alone reads them: suite-wide runs under one form)."""
+        if forms is None:
+            if not hasattr(lib, "nvx_debug_set_forms"):      # an older build loaded through NAVTEX_AMD_LIB: it reads them itself
+                return
+            forms = tuple(int(os.environ.get(name, -1)) for name in ("NVX_INDEPENDENT", "NVX_DYNAMIC_PREROLL", "NVX_DEMOD_TILES"))
+        if tuple(forms) != (-1, -1, -1):
+            self.set_forms(*forms)
 
 
 class Pipeline(HandleStats):
@@ -245,7 +265,7 @@ class Pipeline(HandleStats):
                  chain_masks: Optional[Iterable[int]] = None, labels: Optional[Sequence[Sequence[int]]] = None,
                  max_frames: int = 1, char_layer: bool = True, push_mode: bool = False, device: int = 0,
                  wideband: bool = False, bit_history: int = 0, store: "Optional[Store]" = None, stage0_order: int = 1,
-                 eager_launch: bool = False, stall_timeout_ms: int = 0):
+                 eager_launch: bool = False, stall_timeout_ms: int = 0, forms: Optional[Sequence[int]] = None):
         self.messages: List[Tuple[int, int, str, str]] = []          # (stream, freq, bbbb, text)
         cfg = N.Config()
         lib.nvx_config_default(C.byref(cfg))
@@ -277,6 +297,7 @@ class Pipeline(HandleStats):
         N.check(lib.nvx_create(C.byref(cfg), C.byref(h)), "nvx_create")
         self._h = h
         self._bits = {}
+        self._apply_forms(forms)
 
     # host input ---------------------------------------------------------
     def push(self, stream: int, iq: np.ndarray) -> None:
@@ -461,7 +482,8 @@ class Group:
 
     def __init__(self, devices: Sequence[int], n_streams: int, raw_rate: bool = False, chain_mask: int = CHAIN_518 | CHAIN_490,
                  chain_masks: Optional[Iterable[int]] = None, labels: Optional[Sequence[Sequence[int]]] = None, max_frames: int = 1,
-                 char_layer: bool = True, push_mode: bool = False, host_threads: int = 0):
+                 char_layer: bool = True, push_mode: bool = False, host_threads: int = 0,
+                 forms: Optional[Sequence[int]] = None):
         self.messages: List[Tuple[int, int, str, str]] = []          # (global stream, freq, bbbb, text)
         cfg = N.Config()
         lib.nvx_config_default(C.byref(cfg))
@@ -487,6 +509,7 @@ class Group:
             d, f, n = C.c_int(), C.c_int(), C.c_int()
             N.check(lib.nvx_group_member(g, m, C.byref(d), C.byref(f), C.byref(n), None), "nvx_group_member")
             self.members.append((d.value, f.value, n.value))
+            self.member_view(m)._apply_forms(forms)
         self._bits = {}
 
     def member_of(self, stream: int) -> int:

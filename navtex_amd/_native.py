@@ -69,6 +69,7 @@ def _load() -> C.CDLL:
         "nvx_last_error": (C.c_char_p, []), "nvx_version": (C.c_char_p, []), "nvx_abi_version": (i, []),
         "nvx_sample_to_int16": (i, [C.c_double, C.POINTER(C.c_int16)]), "nvx_shim_stats": (i, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
         "nvx_debug_advance_clock": (i, [vp, i, C.c_uint64]),
+        "nvx_debug_set_forms": (i, [vp, i, i, i]), "nvx_debug_last_forms": (i, [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "init_fir_filter1": (None, []), "sample_in_1": (None, [C.c_double, C.c_double]), "init_fir2_wrapper": (None, []),
         "nvx_set_trace": (i, [vp, SITOR_TRACE_FN, vp]),
         "nvx_shim_latency": (i, [C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), i]),

@@ -466,6 +466,9 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     da.corr = h->d_corr; da.csum = h->d_csum;
     da.sig = h->sig_on ? r.d_sig : nullptr; da.sig_part = h->d_sig_part; da.sig_stride = h->sig_stride;
     da.soft = h->soft_mode ? r.d_soft : nullptr; da.soft_cap = std::min(h->soft_cap, n3_full / 8 + 8); da.soft_pos = h->d_soft_pos;
+    nvx_forms forms = h->forms_req;                     // the request in, what the launchers took out
+    forms.demod_tiles = nvx_front_tile_wgs(&da, forms.demod_tiles);
+    da.sig_parts = 1 + forms.demod_tiles;
 
     // cascade on `st`: it may not overwrite y3[yb] before the demodulator of two launches ago has read it
     if (h->demod_pending[yb]) HIP_TRY(hipStreamWaitEvent(st, h->demod_done[yb], 0));
@@ -481,7 +484,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
         wa.y3 = h->d_y3[yb]; wa.y3_cap = (size_t)h->y3_cap; wa.y3_base = 0;
         wa.queue = h->d_ctrl; wa.status = h->d_ctrl + 1; wa.done = h->d_ctrl + NVX_CASCADE_CTRL_INTS; wa.third0 = third0;
         wa.y2[0] = y2_bufs[0]; wa.y2[1] = y2_bufs[1]; wa.y2_pitch = h->y2_pitch; wa.y2_row = h->d_y2row;
-        HIP_TRY(nvx_launch_wideband_fused(&wa, st));
+        HIP_TRY(nvx_launch_wideband_fused(&wa, &forms, st));
     } else {
         nvx_cascade_args ca{};
         ca.iq = (const uint32_t *)d_iq; ca.pitch = pitch; ca.first_sample = first_sample;
@@ -493,7 +496,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
         ca.third0 = third0;
         ca.tune_k = h->d_tune_k;
         ca.max_waves_per_cu = -1;                        // one fewer than fit: room for the previous launch's demodulator (above)
-        HIP_TRY(nvx_launch_cascade(&ca, h->cascade_raw, h->nch, st));
+        HIP_TRY(nvx_launch_cascade(&ca, h->cascade_raw, h->nch, &forms, st));
     }
     if (r.timed) HIP_TRY(hipEventRecord(r.ev[1], st));
     HIP_TRY(hipMemcpyAsync(h->h_status + NVX_STATUS_INTS * (h->launched % RESULT_SLOTS), h->d_ctrl + 1, NVX_STATUS_INTS * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -541,6 +544,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     r.g0_all = h->g0s[0];
     h->launched++;
     h->last_n3 = n3_full;
+    h->forms_last = forms; h->forms_known = true;
     for (int i = 0; i < n_here; i++) {                   // the participants have moved on: other block, n3 more samples
         const int s = with_list ? r.h_part[i].stream : i;
         h->parity[s] ^= 1; h->g0s[s] += (unsigned long long)(tail_n3 ? tail_n3[i] : n3_full);
@@ -1095,6 +1099,26 @@ extern "C" int nvx_debug_advance_clock(nvx_handle *h, int stream, uint64_t perio
     HIP_TRY(hipMemcpy(entry, seal, sizeof seal, hipMemcpyHostToDevice));
     h->g0s[stream] = g_new;
     h->diverged = !streams_together(h);
+    return NVX_OK;
+}
+
+extern "C" int nvx_debug_set_forms(nvx_handle *h, int independent, int dynamic_preroll, int demod_tiles)
+{
+    const auto bad = [](int v) { return v < -1 || v > 1; };
+    if (!h || bad(independent) || bad(dynamic_preroll) || bad(demod_tiles)) { nvx_set_error("nvx_debug_set_forms: null handle, or a value outside -1 (automatic), 0, 1"); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->forms_req = nvx_forms{ independent, dynamic_preroll, demod_tiles };
+    return NVX_OK;
+}
+
+extern "C" int nvx_debug_last_forms(nvx_handle *h, int *independent, int *dynamic_preroll, int *front_tile_wgs)
+{
+    if (!h) { nvx_set_error("nvx_debug_last_forms: null handle"); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (!h->forms_known) { nvx_set_error("nvx_debug_last_forms: the handle has launched nothing yet"); return NVX_ERR_STATE; }
+    if (independent) *independent = h->forms_last.independent;
+    if (dynamic_preroll) *dynamic_preroll = h->forms_last.dynamic_preroll;
+    if (front_tile_wgs) *front_tile_wgs = h->forms_last.demod_tiles;
     return NVX_OK;
 }
 

@@ -475,11 +475,9 @@ template <> struct CascadeKernel<true, 2, 3, false> { static constexpr auto fn =
 // launcher (C linkage, called from the host runtime)
 // ===========================================================================
 #define NVX_MAX_DEVICES 64
-// test switches: both unit forms ship and the launcher picks one per launch; the suite forces each (read once per process)
-static int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
-
+// both unit forms ship and the launcher picks one per launch; *f carries a forced choice in and the choice taken out
 template <bool RAW, int NCH, int S0 = 1, bool LIST = false>
-static hipError_t launch_cascade_as(const nvx_cascade_args *a, hipStream_t s)
+static hipError_t launch_cascade_as(const nvx_cascade_args *a, nvx_forms *f, hipStream_t s)
 {
     // persistent grid: as many single-wave workgroups as the device of this launch holds at once (cached per device:
     // handles on different devices, and launches from different threads, share this function)
@@ -510,9 +508,8 @@ static hipError_t launch_cascade_as(const nvx_cascade_args *a, hipStream_t s)
     nvx_cascade_args args = *a;
     // Fewer streams than resident waves: the units of one stream would run one after the other and most of the
     // chip would idle.  Then every unit rebuilds its filter histories from the nine passes in front of it
-    // (+2.9 % input) and all of them run at once.  NVX_INDEPENDENT=0/1 forces the choice (tests, A/B runs).
-    static const int force = env_int("NVX_INDEPENDENT", -1);
-    args.independent = force >= 0 ? force : (a->n_streams < resident && a->n_frames > 1);
+    // (+2.9 % input) and all of them run at once.
+    args.independent = f->independent >= 0 ? f->independent : (a->n_streams < resident && a->n_frames > 1);
     // The last frame of a launch goes out in thirds when the launch is longer than one round of the grid: the waves that
     // get no unit in the last round idle for a third of a frame instead of a whole one (4096 x 12: 4.1 % of all wave
     // time was that idle tail).  r3: a launch of independent units that leaves two thirds of the chip idle even so -- one
@@ -524,9 +521,9 @@ static hipError_t launch_cascade_as(const nvx_cascade_args *a, hipStream_t s)
     const long long units = (long long)a->n_streams * (args.split_from + 3LL * split_frames);
     const unsigned grid = (unsigned)(units < resident ? units : resident);
     // hand-over launches: a unit whose predecessor is still running rebuilds its histories instead of waiting for it
-    // (NVX_DYNAMIC_PREROLL=0: it waits, as in round 1)
-    static const int dynamic = env_int("NVX_DYNAMIC_PREROLL", 1);
-    args.dynamic_preroll = dynamic != 0;
+    // (forced off: it waits, as in round 1)
+    args.dynamic_preroll = f->dynamic_preroll != 0;
+    f->independent = args.independent; f->dynamic_preroll = args.dynamic_preroll;
     hipLaunchKernelGGL((CascadeKernel<RAW, NCH, S0, LIST>::fn), dim3(grid), dim3(64), 0, s, args);
     return hipGetLastError();
 }
@@ -557,7 +554,7 @@ static hipError_t tune_table_ready()
     return e;
 }
 
-extern "C" hipError_t nvx_launch_cascade(const nvx_cascade_args *a, int raw, int nch, hipStream_t s)
+extern "C" hipError_t nvx_launch_cascade(const nvx_cascade_args *a, int raw, int nch, nvx_forms *f, hipStream_t s)
 {
     { hipError_t e = tune_table_ready(); if (e != hipSuccess) return e; }
     // queue counter, status word and per-stream completion counts start at zero every launch
@@ -565,11 +562,11 @@ extern "C" hipError_t nvx_launch_cascade(const nvx_cascade_args *a, int raw, int
     if (e != hipSuccess) return e;
     const bool cic3 = raw && a->stage0_order == 3;
     if (a->part) {
-        if (cic3) return nch == 1 ? launch_cascade_as<true, 1, 3, true>(a, s) : launch_cascade_as<true, 2, 3, true>(a, s);
-        if (raw) return nch == 1 ? launch_cascade_as<true, 1, 1, true>(a, s) : launch_cascade_as<true, 2, 1, true>(a, s);
-        return nch == 1 ? launch_cascade_as<false, 1, 1, true>(a, s) : launch_cascade_as<false, 2, 1, true>(a, s);
+        if (cic3) return nch == 1 ? launch_cascade_as<true, 1, 3, true>(a, f, s) : launch_cascade_as<true, 2, 3, true>(a, f, s);
+        if (raw) return nch == 1 ? launch_cascade_as<true, 1, 1, true>(a, f, s) : launch_cascade_as<true, 2, 1, true>(a, f, s);
+        return nch == 1 ? launch_cascade_as<false, 1, 1, true>(a, f, s) : launch_cascade_as<false, 2, 1, true>(a, f, s);
     }
-    if (cic3) return nch == 1 ? launch_cascade_as<true, 1, 3>(a, s) : launch_cascade_as<true, 2, 3>(a, s);
-    if (raw) return nch == 1 ? launch_cascade_as<true, 1>(a, s) : launch_cascade_as<true, 2>(a, s);
-    return nch == 1 ? launch_cascade_as<false, 1>(a, s) : launch_cascade_as<false, 2>(a, s);
+    if (cic3) return nch == 1 ? launch_cascade_as<true, 1, 3>(a, f, s) : launch_cascade_as<true, 2, 3>(a, f, s);
+    if (raw) return nch == 1 ? launch_cascade_as<true, 1>(a, f, s) : launch_cascade_as<true, 2>(a, f, s);
+    return nch == 1 ? launch_cascade_as<false, 1>(a, f, s) : launch_cascade_as<false, 2>(a, f, s);
 }

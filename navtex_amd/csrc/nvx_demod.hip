@@ -641,28 +641,29 @@ __global__ __launch_bounds__(64) void nvx_demod_fsm(nvx_demod_args a)
     else fsm_chain<false>(a, s_tab);
 }
 
-// Which form of the front a launch takes: the number of tile workgroups per chain (the tile-parallel form), or 0 (the walk)
-static int front_tile_wgs(const nvx_demod_args *a)
+// Which form of the front a launch takes: the number of tile workgroups per chain (the tile-parallel form), or 0 (the
+// walk); request: -1 = the rule below, 0 / 1 = the walk / tiles wherever a launch has enough of them
+extern "C" int nvx_front_tile_wgs(const nvx_demod_args *a, int request)
 {
     const unsigned chains = a->part ? (unsigned)(2 * a->per_part * a->n_part) : (unsigned)a->n_slots;
-    // Few chains and a long launch: one workgroup per tile instead of one per chain (NVX_DEMOD_TILES=0/1 forces the
-    // choice: tests, A/B runs).  Otherwise the walk: the tile form does 2.3 x the arithmetic in workgroups of 29 KB of
+    // Few chains and a long launch: one workgroup per tile instead of one per chain.
+    // Otherwise the walk: the tile form does 2.3 x the arithmetic in workgroups of 29 KB of
     // LDS, which find no room on a CU beside the persistent grid of the NEXT cascade launch -- the demodulator runs
     // beside it -- once that grid fills the chip (64 streams x 62 frames: step 3.1 ms with tiles, cascade + demodulator
     // one after the other).  So: only while the launch's own cascade units (at most chains x frames) leave the chip
     // at least half empty.
-    static const int force = getenv("NVX_DEMOD_TILES") ? atoi(getenv("NVX_DEMOD_TILES")) : -1;
     const int tiles = (a->n3 + DTL - 1) / DTL;
     const long long chain_frames = (long long)chains * (a->n3 / NVX_Y3_PER_FRAME);
     // (the tile form works on a.n3: every chain whole frames.  A launch that ends streams is one frame long: the walk.)
-    const bool parallel = tiles >= 3 && (force >= 0 ? force != 0 : chain_frames <= 2560);
+    const bool parallel = tiles >= 3 && (request >= 0 ? request != 0 : chain_frames <= 2560);
     return parallel ? tiles - 2 : 0;                         // one workgroup per tile from the third on; the head walks the first two
 }
 
 extern "C" hipError_t nvx_launch_demod_front(const nvx_demod_args *a, hipStream_t s)
 {
     const unsigned chains = a->part ? (unsigned)(2 * a->per_part * a->n_part) : (unsigned)a->n_slots;
-    const int wgs = front_tile_wgs(a);
+    const int wgs = a->sig_parts - 1;
+    if (wgs < 0) return hipErrorInvalidValue;                                 // the caller has not chosen the form
     if (a->sig && 1 + wgs > a->sig_stride) return hipErrorInvalidValue;      // the partials would not fit their buffer
     if (wgs) {
         hipLaunchKernelGGL(nvx_demod_front_head, dim3(chains), dim3(NVX_FRONT_THREADS), 0, s, *a);
@@ -676,9 +677,8 @@ extern "C" hipError_t nvx_launch_demod_front(const nvx_demod_args *a, hipStream_
 extern "C" hipError_t nvx_launch_demod_fsm(const nvx_demod_args *a, hipStream_t s)
 {
     const int chains = a->part ? 2 * a->per_part * a->n_part : a->n_slots;
-    nvx_demod_args b = *a;
-    b.sig_parts = 1 + front_tile_wgs(a);                 // as nvx_launch_demod_front chose
-    hipLaunchKernelGGL(nvx_demod_fsm, dim3((unsigned)((chains + 63) / 64)), dim3(64), 0, s, b);
+    if (a->sig_parts < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nvx_demod_fsm, dim3((unsigned)((chains + 63) / 64)), dim3(64), 0, s, *a);
     return hipGetLastError();
 }
 

@@ -208,6 +208,10 @@ struct nvx_handle {
     int n_arrival = 0;
     uint64_t launched = 0, collected = 0;
     int last_n3 = 0;
+    // kernel forms (nvx_debug_set_forms): the request every launch passes to the launchers -- configuration, as cfg -- and
+    // what they took for the most recently enqueued launch (forms_known: there has been one)
+    nvx_forms forms_req = { -1, -1, -1 }, forms_last = { -1, -1, -1 };
+    bool forms_known = false;
     // timing
     bool timing = false;
     float ms[4] = { 0.f, 0.f, 0.f, 0.f };   // last collected launch: cascade, demodulator (front + FSM), nvx_fir3, the FSM kernel alone

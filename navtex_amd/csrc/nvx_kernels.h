@@ -185,7 +185,8 @@ typedef struct {
     nvx_sig_rec *sig;          /* signal reports on: [n_slots] records of this launch, folded by nvx_demod_fsm; NULL = off */
     nvx_sig_rec *sig_part;     /* [n_slots][sig_stride] partial records of the front's workgroups, in tile order          */
     int sig_stride;            /* partials per slot the buffer holds (the launcher refuses a launch that needs more)       */
-    int sig_parts;             /* set by the launchers: partials per slot this launch writes (1 = the walk)                */
+    int sig_parts;             /* the form of the front, set by the caller: 1 + nvx_front_tile_wgs = partials per slot this */
+                               /* launch writes (1 = the walk); both demodulator launchers go by it                        */
     /* soft decisions (navtex_amd_soft.h): per decided bit Brot - Yrot of its window, float32, in bit order beside the bits */
     float *soft;               /* soft values on: [n_slots][soft_cap], written by nvx_demod_fsm; NULL = off                */
     int soft_cap;              /* values per slot this launch's rows hold (a launch yields as many as bits; what does not  */
@@ -233,13 +234,23 @@ typedef struct {
     double2 *y2[2]; size_t y2_pitch; const int *y2_row;     /* as nvx_fir3_args (rows by decoded stream * 2 + chain)     */
 } nvx_wideband_args;
 
+/* The kernel forms of a launch (navtex_amd.h: nvx_debug_set_forms, nvx_debug_last_forms).  A launcher reads its request
+ * here (-1 = automatic, 0 / 1 = forced off / on) and writes back what it took.                                          */
+typedef struct {
+    int independent;           /* cascade and fused wideband kernels: units pre-roll instead of handing over              */
+    int dynamic_preroll;       /* cascade kernels: a unit whose predecessor still runs pre-rolls instead of waiting        */
+    int demod_tiles;           /* the demodulator's front; taken: tile workgroups per chain (0 = the walk)                 */
+} nvx_forms;
+
 #ifdef __cplusplus
 extern "C" {
 #endif
-hipError_t nvx_launch_wideband_fused(const nvx_wideband_args *a, hipStream_t s);
+hipError_t nvx_launch_wideband_fused(const nvx_wideband_args *a, nvx_forms *f, hipStream_t s);
 hipError_t nvx_launch_channelise(const nvx_channelise_args *a, hipStream_t s);
-hipError_t nvx_launch_cascade(const nvx_cascade_args *a, int raw, int nch, hipStream_t s);
+hipError_t nvx_launch_cascade(const nvx_cascade_args *a, int raw, int nch, nvx_forms *f, hipStream_t s);
 hipError_t nvx_launch_fir3(const nvx_fir3_args *a, hipStream_t s);
+/* the form of the front for a launch: tile workgroups per chain (the tile-parallel form), or 0 (the walk) */
+int nvx_front_tile_wgs(const nvx_demod_args *a, int request);
 hipError_t nvx_launch_demod_front(const nvx_demod_args *a, hipStream_t s);
 hipError_t nvx_launch_demod_fsm(const nvx_demod_args *a, hipStream_t s);
 hipError_t nvx_launch_synth(const nvx_synth_args *a, int n_streams, hipStream_t s);

@@ -223,7 +223,7 @@ __device__ __forceinline__ void wideband_main(const nvx_wideband_args &a)
 
 __global__ __launch_bounds__(512) void nvx_wideband_fused(nvx_wideband_args a) { wideband_main(a); }
 
-extern "C" hipError_t nvx_launch_wideband_fused(const nvx_wideband_args *a, hipStream_t s)
+extern "C" hipError_t nvx_launch_wideband_fused(const nvx_wideband_args *a, nvx_forms *f, hipStream_t s)
 {
     // persistent grid: as many 8-wave workgroups as the device of this launch holds at once (LDS: one per CU)
     static std::mutex mu;
@@ -248,10 +248,10 @@ extern "C" hipError_t nvx_launch_wideband_fused(const nvx_wideband_args *a, hipS
     if (e != hipSuccess) return e;
     const long long units = (long long)a->n_wide * a->n_frames;
     // Fewer streams than resident workgroups: independent units (pre-roll instead of hand-over), all frames at once.
-    // NVX_INDEPENDENT=0/1 forces the choice (tests, A/B runs), as for the cascade kernel.
+    // *f carries a forced choice in and the choice taken out, as for the cascade kernel.
     nvx_wideband_args args = *a;
-    static const int force = getenv("NVX_INDEPENDENT") ? atoi(getenv("NVX_INDEPENDENT")) : -1;
-    args.independent = force >= 0 ? force : (a->n_wide < resident && a->n_frames > 1);
+    args.independent = f->independent >= 0 ? f->independent : (a->n_wide < resident && a->n_frames > 1);
+    f->independent = args.independent; f->dynamic_preroll = -1;      // (no unit of this kernel pre-rolls dynamically)
     // ... and in thirds when even that leaves two thirds of the chip idle (one RSP capture replayed)
     args.thirds = args.independent && 3 * units <= resident;
     const long long all_units = units * (args.thirds ? 3 : 1);

@@ -106,9 +106,10 @@ hipError_t hipMemset2DAsync(void *d, size_t pitch, int v, size_t w, size_t rows,
 }
 // none of the calls under test launches anything
 extern "C" {
-hipError_t nvx_launch_wideband_fused(const nvx_wideband_args *, hipStream_t) { g_bad++; return hipErrorUnknown; }
-hipError_t nvx_launch_cascade(const nvx_cascade_args *, int, int, hipStream_t) { g_bad++; return hipErrorUnknown; }
+hipError_t nvx_launch_wideband_fused(const nvx_wideband_args *, nvx_forms *, hipStream_t) { g_bad++; return hipErrorUnknown; }
+hipError_t nvx_launch_cascade(const nvx_cascade_args *, int, int, nvx_forms *, hipStream_t) { g_bad++; return hipErrorUnknown; }
 hipError_t nvx_launch_fir3(const nvx_fir3_args *, hipStream_t) { g_bad++; return hipErrorUnknown; }
+int nvx_front_tile_wgs(const nvx_demod_args *, int) { return 0; }
 hipError_t nvx_launch_demod_front(const nvx_demod_args *, hipStream_t) { g_bad++; return hipErrorUnknown; }
 hipError_t nvx_launch_demod_fsm(const nvx_demod_args *, hipStream_t) { g_bad++; return hipErrorUnknown; }
 int add_message(char *, char *, int) { g_bad++; return 0; }

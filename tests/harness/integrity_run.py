@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """TEST INFRASTRUCTURE (uses the oracle): every kernel family that hands filter state from work unit to work unit, with the
-hand-over form forced (NVX_INDEPENDENT=0), complete 900 S/s output and bits against the oracle, and the seal counters of
-nvx_cascade_integrity_stats.  Run in a process of its own by tests/test_gpu_integrity.py -- with the shipped library (no
+hand-over form forced (argument: "waiting" or "prerolling" units; every handle's last launch is held to it), complete
+900 S/s output and bits against the oracle, and the seal counters of nvx_cascade_integrity_stats.
+Run in a process of its own by tests/test_gpu_integrity.py -- with the shipped library (no
 stale hand-over may be seen) and with the fault-injection build tests/_variants/libnavtex_amd_inject.so
 (NAVTEX_AMD_LIB; -DNVX_INJECT_STALE=n: every n-th hand-over reads the block of the stream's previous launch instead -- the
 seal must catch each one, the pre-roll must repair it, and nothing may change in the output).  Prints one JSON line."""
@@ -19,7 +20,7 @@ import oracle_binding as ob
 import signals
 import tune_ref
 
-assert os.environ.get("NVX_INDEPENDENT") == "0", "run with NVX_INDEPENDENT=0: the hand-over form is the one under test"
+FORMS = {"waiting": signals.HANDOVER_WAITING, "prerolling": signals.HANDOVER_PREROLLING}[sys.argv[1]]    # the hand-over form is the one under test
 out = {"lib": os.environ.get("NAVTEX_AMD_LIB", "shipped"), "cases": []}
 
 
@@ -49,7 +50,7 @@ for raw, masks, order in ((False, [1, 2, 1], 1), (False, [3, 1, 3], 1), (True, [
             r.push(iqs[s])
         refs.append(r)
     ok = True
-    with nv.Pipeline(n_streams=S, raw_rate=raw, chain_masks=masks, max_frames=7, char_layer=False, stage0_order=order) as p:
+    with nv.Pipeline(n_streams=S, raw_rate=raw, chain_masks=masks, max_frames=7, char_layer=False, stage0_order=order, forms=FORMS) as p:
         got = {(s, c): [] for s in range(S) for c in range(2) if (masks[s] >> c) & 1}
         f0 = 0
         for k in (7, 3, 6, 4):
@@ -59,6 +60,7 @@ for raw, masks, order in ((False, [1, 2, 1], 1), (False, [3, 1, 3], 1), (True, [
                 got[key].append(p.debug_y3(*key)[: k * nv.FRAME_Y3].copy())
         for (s, c), parts in got.items():
             ok = ok and np.array_equal(u64(np.concatenate(parts)), u64(refs[s].y3(c))) and p.bits(s, c) == refs[s].bits(c) and len(refs[s].bits(c)) > 300
+        signals.assert_cascade_form(p, FORMS)
         stale, failed, launches = p.integrity_stats()
     buf.free()
     out["cases"].append(dict(kind="resident", raw=raw, masks=masks, order=order, ok=bool(ok), stale=stale, failed=failed, launches=launches))
@@ -91,7 +93,7 @@ for raw, masks, order, tune in ((False, [3, 1, 3], 1, {(0, 0): 960, (0, 1): -288
             if (s, c) in ks:
                 want[(s, c)] = tune_ref.chain(y1, c, ks[(s, c)])
     ok = True
-    with nv.Pipeline(n_streams=S, raw_rate=raw, chain_masks=masks, max_frames=7, char_layer=False, stage0_order=order) as p:
+    with nv.Pipeline(n_streams=S, raw_rate=raw, chain_masks=masks, max_frames=7, char_layer=False, stage0_order=order, forms=FORMS) as p:
         for (s, c), kc in tune.items():
             ok = ok and p.set_carrier(s, c, kc * tune_ref.STEP_HZ) == kc * tune_ref.STEP_HZ
         ok = ok and [p.carrier(*key)[1] for key in chains] == [key not in tune for key in chains]
@@ -105,6 +107,7 @@ for raw, masks, order, tune in ((False, [3, 1, 3], 1, {(0, 0): 960, (0, 1): -288
         for key, parts in got.items():
             bits = tune_ref.decode(want[key])
             ok = ok and want[key].shape[0] == F * nv.FRAME_Y3 and np.array_equal(u64(np.concatenate(parts)), u64(want[key])) and p.bits(*key) == bits and len(bits) > 300
+        signals.assert_cascade_form(p, FORMS)
         stale, failed, launches = p.integrity_stats()
     buf.free()
     out["cases"].append(dict(kind="resident", tuned=True, raw=raw, masks=masks, order=order, ok=bool(ok), stale=stale, failed=failed, launches=launches))
@@ -113,7 +116,7 @@ for raw, masks, order, tune in ((False, [3, 1, 3], 1, {(0, 0): 960, (0, 1): -288
 from test_gpu_independent_streams import ragged_case
 for seed in (1, 2, 3, 4, 5, 6, 7, 8, 11, 12):
     try:
-        info = ragged_case(nv, ob, seed)
+        info = ragged_case(nv, ob, seed, forms=FORMS)
         info["ok"] = True
     except AssertionError as e:
         info = dict(seed=seed, ok=False, error=str(e)[:200], stale_repaired=-1)
@@ -135,7 +138,7 @@ for raw, masks, order in ((False, [1, 2, 1, 1], 1), (False, [3, 1, 2, 3], 1), (T
             r.push(iqs[s])
         refs.append(r)
     ok = True
-    with nv.Pipeline(n_streams=S, raw_rate=raw, chain_masks=masks, max_frames=6, push_mode=True, char_layer=False, stage0_order=order) as p:
+    with nv.Pipeline(n_streams=S, raw_rate=raw, chain_masks=masks, max_frames=6, push_mode=True, char_layer=False, stage0_order=order, forms=FORMS) as p:
         p.set_active(2, False)
         for half in range(2):
             for s in (0, 1, 3):
@@ -146,6 +149,7 @@ for raw, masks, order in ((False, [1, 2, 1, 1], 1), (False, [3, 1, 2, 3], 1), (T
         for s in range(S):
             for c in range(2):
                 ok = ok and p.bits(s, c) == (refs[s].bits(c) if (masks[s] >> c) & 1 else "")
+        signals.assert_cascade_form(p, FORMS)
         stale, failed, launches = p.integrity_stats()
     out["cases"].append(dict(kind="list", deep=True, raw=raw, masks=masks, order=order, ok=bool(ok), stale=stale, failed=failed, launches=launches, partial_launches=partial))
 
@@ -170,7 +174,7 @@ for w in range(W):
 buf = nv.DeviceBuffer(W * n * 4)
 buf.upload(raw)
 ok = True
-with nv.Pipeline(n_streams=W, wideband=True, chain_mask=3, max_frames=F, char_layer=False) as p:
+with nv.Pipeline(n_streams=W, wideband=True, chain_mask=3, max_frames=F, char_layer=False, forms=FORMS) as p:
     stale_total = 0
     for plan in ([F], [5, 7]):
         p.reset()
@@ -183,6 +187,7 @@ with nv.Pipeline(n_streams=W, wideband=True, chain_mask=3, max_frames=F, char_la
                 got[key].append(p.debug_y3(*key)[: k * nv.FRAME_Y3].copy())
         for key, (y3, bits) in want.items():
             ok = ok and np.array_equal(u64(np.concatenate(got[key])), y3) and p.bits(*key) == bits
+    assert p.last_forms()[0] == 0, p.last_forms()
     stale, failed, launches = p.integrity_stats()
 buf.free()
 out["cases"].append(dict(kind="wideband_fused", ok=bool(ok), stale=stale, failed=failed, launches=launches))

@@ -23,6 +23,7 @@ int main(void)
     T(nvx_kernel_time_stats(NULL, 0, d, u, 0)); T(nvx_cascade_wait_stats(NULL, u, u + 1, u + 2, 0));
     T(nvx_cascade_integrity_stats(NULL, u, u + 1, u + 2, 0)); T(nvx_demod_tie_stats(NULL, u, u + 1, d));
     T(nvx_enable_debug(NULL, 1)); T(nvx_debug_cascade_state(NULL, 0, buf, 16, 0)); T(nvx_debug_advance_clock(NULL, 0, 1));
+    T(nvx_debug_set_forms(NULL, -1, -1, -1)); T(nvx_debug_last_forms(NULL, NULL, NULL, NULL));
     T(nvx_debug_y3(NULL, 0, 0, d, 2)); T(nvx_debug_dphi(NULL, 0, 0, d, 2));
     T((long long)(size_t)nvx_handle_stream(NULL));
     T(nvx_decode_wav(NULL, 0, "x.wav"));

@@ -33,3 +33,24 @@ def stream_params(nv, stream_id: int, rate: int, freq_hz: int = 14000, n_phasing
     off = (mix32(h ^ 0xA5A5A5A5) % spb) | 1
     return nv.make_stream([dict(freq_hz=freq_hz, bits=bits, bit_offset=off % spb, phase0=mix32(h ^ 0x3C3C3C3C),
                                 amplitude=amplitude)], seed=h, noise_amp=noise_amp), bits
+
+
+# Kernel forms a test forces with Pipeline(forms=...): (independent, dynamic_preroll, demod_tiles), -1 = automatic.
+# The cascade's three ways to carry filter state across the frames of a launch: hand-over where a unit waits for its
+# predecessor (round 1's form), hand-over where a unit whose predecessor is still running pre-rolls instead (the default;
+# with few streams nearly every unit does), every unit independent.
+HANDOVER_WAITING, HANDOVER_PREROLLING, INDEPENDENT, AUTOMATIC = (0, 0, -1), (0, 1, -1), (1, -1, -1), (-1, -1, -1)
+CASCADE_FORMS = (HANDOVER_WAITING, HANDOVER_PREROLLING, INDEPENDENT)
+WALK, TILES = (-1, -1, 0), (-1, -1, 1)
+
+
+def assert_cascade_form(p, forms):
+    """The handle's last launch took the cascade form that `forms` forces (nvx_debug_last_forms)."""
+    got = p.last_forms()
+    assert all(want < 0 or have == want for have, want in zip(got[:2], forms[:2])), f"forms {forms} asked for, {got} ran"
+
+
+def assert_front_form(p, forms, tiles_fit):
+    """... and the front form: tile workgroups where `forms` forces tiles and the launch has enough of them, else the walk."""
+    wgs = p.last_forms()[2]
+    assert (wgs > 0) == (forms[2] == 1 and tiles_fit), f"forms {forms} asked for, {wgs} tile workgroups per chain ran"

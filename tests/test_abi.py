@@ -144,3 +144,22 @@ def test_product_never_touches_the_oracle():
             assert "nvx_oracle" not in text and "nvxo_" not in text and "oracle_binding" not in text, path
     out = subprocess.run(["ldd", str(ROOT / "navtex_amd" / "libnavtex_amd.so")], capture_output=True, text=True).stdout
     assert "oracle" not in out
+
+
+def test_kernel_forms_are_no_environment_matter():
+    """Which form of a kernel a launch takes comes from the handle (nvx_debug_set_forms), not from the process environment:
+    the library does not hold the names the Python binding still honours."""
+    blob = (ROOT / "navtex_amd" / "libnavtex_amd.so").read_bytes()
+    for name in (b"NVX_INDEPENDENT", b"NVX_DYNAMIC_PREROLL", b"NVX_DEMOD_TILES"):
+        assert name not in blob, name
+
+
+def test_every_environment_variable_the_library_reads_is_documented():
+    """Every name a getenv("...") in navtex_amd/csrc reads has a row in the table of INTEGRATION.md section 6."""
+    read = set()
+    for path in (ROOT / "navtex_amd" / "csrc").iterdir():
+        read |= set(re.findall(r'getenv\("(\w+)"\)', path.read_text(errors="replace")))
+    section = (ROOT / "INTEGRATION.md").read_text().split("## 6. Environment switches")[1]
+    rows = set(re.findall(r"^\| `(\w+)` \|", section, flags=re.M))
+    assert read and read <= rows, sorted(read - rows)
+    assert {"NVX_HOST_THREADS", "NVX_GROUP_NUMA", "NAVTEX_AMD_DEVICE"} <= read

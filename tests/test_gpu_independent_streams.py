@@ -220,13 +220,14 @@ def test_wideband_streams_advance_independently(nv, oracle):
         assert got == want and all(len(b) > 50 for b in want)
 
 
-def ragged_case(nv, oracle, seed, tails=False):
+def ragged_case(nv, oracle, seed, tails=False, forms=None):
     """Random handles (stream count, chain masks, input rate, stage-0 order, max_frames) fed in random order with random
     chunk sizes, streams going silent for a while (explicitly inactive, or simply not fed until another stream's staging
     fills), a reset-free flush in the middle: every list kernel (252 kS/s and raw rate, one and two chains, both stage-0
     forms) meets partial launches, per-stream parities and per-stream sample counts.  Every chain == the oracle.
     tails: every stream's input also ends with a ragged tail of its own (some empty, some shorter than one 900 S/s sample)
-    and the handle is ended with nvx_finish instead of flushed: the bits are the oracle's on exactly those samples."""
+    and the handle is ended with nvx_finish instead of flushed: the bits are the oracle's on exactly those samples.
+    forms: the kernel forms to force (Pipeline(forms=...)); the last launch is held to them."""
     rng = np.random.default_rng(1000 + seed)
     raw = bool(rng.integers(0, 2))
     order = int(rng.choice([1, 3])) if raw else 1
@@ -254,7 +255,7 @@ def ragged_case(nv, oracle, seed, tails=False):
             total[s] += t
             st = nv.make_stream([], seed=seed * 100 + s + 50, noise_amp=3000)
             if t: iqs[s] = np.vstack([iqs[s], nv.synth_host(st, rate, t)])
-    with nv.Pipeline(n_streams=S, raw_rate=raw, chain_masks=masks, max_frames=maxf, push_mode=True, char_layer=False, stage0_order=order) as p:
+    with nv.Pipeline(n_streams=S, raw_rate=raw, chain_masks=masks, max_frames=maxf, push_mode=True, char_layer=False, stage0_order=order, forms=forms) as p:
         pos = [0] * S
         asleep = {}                                             # stream -> pushes (of others) until it wakes
         flushed = False
@@ -277,6 +278,8 @@ def ragged_case(nv, oracle, seed, tails=False):
                 p.flush(); flushed = True
         if tails: p.finish()
         else: p.flush()
+        if forms is not None:
+            signals.assert_cascade_form(p, forms)
         partial = p.stream_stats(0)[2]
         stale = p.integrity_stats()[0]
         for s in range(S):
@@ -444,18 +447,18 @@ def test_randomized_ragged_wideband_inputs(nv, oracle, seed):
 def test_ragged_cases_with_the_hand_over_forms_forced(nv, tmp_path):
     """The ragged cases run few streams, so their launches use independent units.  Launches of thousands of streams that
     name their streams hand filter state from unit to unit instead (done[] indexed by list position, state blocks by
-    stream and parity): force that form -- with and without the dynamic pre-roll -- in a subprocess and run cases that
-    between them cover all six list kernels."""
+    stream and parity): force that form -- with and without the dynamic pre-roll -- through the sweep tool (which holds
+    every case's last launch to the form it was given) and run cases that between them cover all six list kernels."""
     import subprocess, sys, os
     root = str(Path(__file__).resolve().parent.parent)
-    for env in (dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="1"), dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="0"), dict(NVX_INDEPENDENT="1")):
-        out = subprocess.run([sys.executable, os.path.join(root, "tools", "gpu_scripts", "sweep_ragged.py"), "1", "20"],
-                             capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
-        assert out.returncode == 0, (env, out.stdout[-1500:], out.stderr[-1500:])
+    for forms in (signals.HANDOVER_PREROLLING, signals.HANDOVER_WAITING, signals.INDEPENDENT):
+        out = subprocess.run([sys.executable, os.path.join(root, "tools", "gpu_scripts", "sweep_ragged.py"), "1", "20", "--forms=" + ",".join(map(str, forms))],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, (forms, out.stdout[-1500:], out.stderr[-1500:])
         last = out.stdout.strip().splitlines()[-1]
         assert last.startswith("20 cases identical to the oracle"), last
         kinds = last[last.index("{"):]
-        assert kinds.count("(") == 6, (env, last)                 # all six (rate, stage-0 order, chains) list kernels were met
+        assert kinds.count("(") == 6, (forms, last)                 # all six (rate, stage-0 order, chains) list kernels were met
 
 
 def test_two_pushers_of_one_stream_take_turns_call_by_call(nv, oracle):

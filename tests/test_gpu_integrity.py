@@ -174,11 +174,12 @@ def test_the_seal_is_sensitive_to_position(nv):
 
 
 def _run(env_extra, waiting_units=True):
-    """tests/harness/integrity_run.py in a process of its own, hand-over form forced; waiting_units: a unit whose predecessor
-    is still running WAITS for it (NVX_DYNAMIC_PREROLL=0), so that every unit but a stream's first takes a hand-over -- with
-    a handful of streams the default (such a unit pre-rolls) leaves few real hand-overs."""
-    env = dict(os.environ, NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="0" if waiting_units else "1", **env_extra)
-    out = subprocess.run([sys.executable, str(ROOT / "tests" / "harness" / "integrity_run.py")], capture_output=True, text=True, timeout=900, env=env)
+    """tests/harness/integrity_run.py in a process of its own (env_extra may name another build of the library), hand-over
+    form forced; waiting_units: a unit whose predecessor is still running WAITS for it (dynamic_preroll = 0), so that every
+    unit but a stream's first takes a hand-over -- with a handful of streams the default (such a unit pre-rolls) leaves
+    few real hand-overs."""
+    out = subprocess.run([sys.executable, str(ROOT / "tests" / "harness" / "integrity_run.py"), "waiting" if waiting_units else "prerolling"],
+                         capture_output=True, text=True, timeout=900, env=dict(os.environ, **env_extra))
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads(out.stdout.strip().splitlines()[-1])
     log = ROOT / "gpurun_out"

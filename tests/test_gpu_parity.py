@@ -2,6 +2,7 @@
 same seeded inputs.  Bar: 900 S/s FIR output bit-exact (fp64 bit patterns),
 'B'/'Y' bits and decoded messages identical; delta-phi within 1 ulp of the
 oracle's glibc atan2 (tolerance explained in DESIGN.md, "atan2")."""
+import hashlib
 from pathlib import Path
 
 import numpy as np
@@ -282,122 +283,124 @@ def test_baud_rate_drift_exercises_the_timing_slew(nv, oracle, baud):
             assert abs(len(want) - nominal * baud / 100.0) < 6 and len(want) != nominal
 
 
-def test_dependent_and_independent_units_agree_bit_for_bit(nv, tmp_path):
+def _units_digest(nv, forms):
+    h = hashlib.sha256()
+    for raw in (False, True):
+        for masks in ([1, 2, 1], [3, 1, 3]):
+            rate = nv.RATE_RAW if raw else nv.RATE_IN
+            frame = nv.FRAME_RAW if raw else nv.FRAME_IN
+            streams = [signals.stream_params(nv, 500 + s, rate)[0] for s in range(3)]
+            pitch = 10 * frame
+            buf = nv.DeviceBuffer(3 * pitch * 4)
+            nv.synth_device(streams, rate, pitch, buf, pitch)
+            with nv.Pipeline(n_streams=3, raw_rate=raw, chain_masks=masks, max_frames=7, char_layer=False, forms=forms) as p:
+                p.process_resident(buf, pitch, 0, 7); p.fetch()
+                signals.assert_cascade_form(p, forms)
+                for s in range(3):
+                    for c in range(2):
+                        if (masks[s] >> c) & 1: h.update(p.debug_y3(s, c).tobytes())
+                p.process_resident(buf, pitch, 7, 3); p.fetch()
+                signals.assert_cascade_form(p, forms)
+                for s in range(3):
+                    for c in range(2):
+                        h.update(p.bits(s, c).encode())
+                        if (masks[s] >> c) & 1: h.update(p.debug_y3(s, c).tobytes())
+            buf.free()
+    return h.hexdigest()
+
+
+def test_dependent_and_independent_units_agree_bit_for_bit(nv):
     """The cascade has two ways to carry filter state across the frames of a launch: hand it from unit
     to unit (many streams) or let every unit rebuild it from the nine passes in front of it (few
-    streams; chosen automatically).  Forced either way in a subprocess, the 900 S/s output and the bits
+    streams; chosen automatically).  Forced either way (signals.CASCADE_FORMS), the 900 S/s output and the bits
     of a 7-frame launch + a 3-frame launch are identical, for both input rates and both kernels."""
-    import hashlib, subprocess, sys, os
-    script = tmp_path / "run.py"
-    script.write_text('''
-import sys, hashlib
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import numpy as np, navtex_amd as nv, signals
-h = hashlib.sha256()
-for raw in (False, True):
-    for masks in ([1, 2, 1], [3, 1, 3]):
-        rate = nv.RATE_RAW if raw else nv.RATE_IN
-        frame = nv.FRAME_RAW if raw else nv.FRAME_IN
-        streams = [signals.stream_params(nv, 500 + s, rate)[0] for s in range(3)]
-        pitch = 10 * frame
-        buf = nv.DeviceBuffer(3 * pitch * 4)
-        nv.synth_device(streams, rate, pitch, buf, pitch)
-        with nv.Pipeline(n_streams=3, raw_rate=raw, chain_masks=masks, max_frames=7, char_layer=False) as p:
-            p.process_resident(buf, pitch, 0, 7); p.fetch()
-            for s in range(3):
-                for c in range(2):
-                    if (masks[s] >> c) & 1: h.update(p.debug_y3(s, c).tobytes())
-            p.process_resident(buf, pitch, 7, 3); p.fetch()
-            for s in range(3):
-                for c in range(2):
-                    h.update(p.bits(s, c).encode())
-                    if (masks[s] >> c) & 1: h.update(p.debug_y3(s, c).tobytes())
-        buf.free()
-print(h.hexdigest())
-''')
-    root = str(Path(__file__).resolve().parent.parent)
-    digests = []
-    # hand-over with waiting units (round 1's form) / hand-over where a unit whose predecessor is still running pre-rolls
-    # instead (the default; with three streams nearly every unit does) / every unit independent
-    for env in (dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="0"), dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="1"), dict(NVX_INDEPENDENT="1")):
-        out = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=300,
-                             env=dict(os.environ, **env))
-        assert out.returncode == 0, out.stderr[-2000:]
-        digests.append(out.stdout.strip().splitlines()[-1])
+    digests = [_units_digest(nv, forms) for forms in signals.CASCADE_FORMS]
     assert digests[0] == digests[1] == digests[2] and len(digests[0]) == 64
 
 
-def test_full_scale_rails_through_the_raw_rate_stage0(nv, tmp_path):
+RAILS_F, RAILS_F2 = 4, 2
+
+
+def _rails_cases(nv, oracle):
+    """(masks, samples, the oracle's pipes) of the one-chain and of the two-chain kernel"""
+    F, F2 = RAILS_F, RAILS_F2
+    n = (F + F2) * nv.FRAME_RAW
+    rng = np.random.default_rng(77)
+    cases = []
+    for masks in ([1, 1, 2], [3, 2, 3]):
+        S = len(masks)
+        raw = rng.integers(-32768, 32768, size=(S, n, 2), dtype=np.int16)
+        for s in range(S):
+            at = 1000 + 977 * s
+            raw[s, at:at + 70000] = 32767                              # both components at the positive rail
+            raw[s, at + 100000:at + 170000] = -32768                   # ... the negative one
+            raw[s, at + 200000:at + 230000, 0] = 32767; raw[s, at + 200000:at + 230000, 1] = -32768
+            alt = np.where(np.arange(40000) & 1, 32767, -32768).astype(np.int16)
+            raw[s, at + 300000:at + 340000, 0] = alt; raw[s, at + 300000:at + 340000, 1] = -1 - alt      # alternating rails, opposite signs
+            # the rails across a frame (= unit) boundary and across the launch boundary
+            raw[s, nv.FRAME_RAW - 5000:nv.FRAME_RAW + 5000] = -32768
+            raw[s, F * nv.FRAME_RAW - 3000:F * nv.FRAME_RAW + 3000] = 32767
+        refs = []
+        for s in range(S):
+            r = oracle.Pipe(chain_mask=masks[s], charlayer=False, tap_y3=(F + F2) * nv.FRAME_Y3)
+            r.push_raw(raw[s])
+            refs.append(r)
+        cases.append((masks, raw, refs))
+    return cases
+
+
+def _rails_run(nv, cases, forms):
+    F, F2 = RAILS_F, RAILS_F2
+    n = (F + F2) * nv.FRAME_RAW
+    checked = 0
+    for masks, raw, refs in cases:
+        S = len(masks)
+        buf = nv.DeviceBuffer(S * n * 4)
+        buf.upload(raw)
+        with nv.Pipeline(n_streams=S, raw_rate=True, chain_masks=masks, max_frames=F, char_layer=False, forms=forms) as p:
+            for f0, k in ((0, F), (F, F2)):
+                p.process_resident(buf, n, f0, k); p.fetch()
+                signals.assert_cascade_form(p, forms)
+                for s in range(S):
+                    for c in range(2):
+                        if (masks[s] >> c) & 1:
+                            want = np.ascontiguousarray(refs[s].y3(c)[f0 * nv.FRAME_Y3:(f0 + k) * nv.FRAME_Y3])
+                            got = p.debug_y3(s, c)
+                            assert got.shape == want.shape and np.array_equal(got.view(np.uint64), want.view(np.uint64)), (masks, s, c, f0)
+                            assert np.abs(want).max() > 10.0
+                            checked += 1
+            for s in range(S):
+                for c in range(2):
+                    assert p.bits(s, c) == (refs[s].bits(c) if (masks[s] >> c) & 1 else ""), (masks, s, c)
+        buf.free()
+    return checked
+
+
+def test_full_scale_rails_through_the_raw_rate_stage0(nv, oracle):
     """The headline kernel's own stage 0 (SDWA half-word adds over the packed int16 pairs, nvx_cascade.hip) at the int16
     rails: uniform random samples over the whole range with stretches of +32767 and of -32768 on both components, mixed
     stretches and alternating rails (the sums of eight reach +-262 144 and round to the rails), through the one-chain and
     the two-chain raw-rate kernels, in the hand-over form (waiting and pre-rolling) and with independent units: the
     complete 900 S/s output as bit patterns and the bits == the oracle's raw-rate pipe (stage replaced:
     receiver/capt_sched.c:412-413, the vendor's /8 decimation; first consumer receiver/fir1cpp.C:80-136)."""
-    import subprocess, sys, os
-    script = tmp_path / "rails.py"
-    script.write_text('''
-import sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import numpy as np, navtex_amd as nv, oracle_binding as ob
-F, F2 = 4, 2
-n = (F + F2) * nv.FRAME_RAW
-rng = np.random.default_rng(77)
-checked = 0
-for masks in ([1, 1, 2], [3, 2, 3]):
-    S = len(masks)
-    raw = rng.integers(-32768, 32768, size=(S, n, 2), dtype=np.int16)
-    for s in range(S):
-        at = 1000 + 977 * s
-        raw[s, at:at + 70000] = 32767                              # both components at the positive rail
-        raw[s, at + 100000:at + 170000] = -32768                   # ... the negative one
-        raw[s, at + 200000:at + 230000, 0] = 32767; raw[s, at + 200000:at + 230000, 1] = -32768
-        alt = np.where(np.arange(40000) & 1, 32767, -32768).astype(np.int16)
-        raw[s, at + 300000:at + 340000, 0] = alt; raw[s, at + 300000:at + 340000, 1] = -1 - alt      # alternating rails, opposite signs
-        # the rails across a frame (= unit) boundary and across the launch boundary
-        raw[s, nv.FRAME_RAW - 5000:nv.FRAME_RAW + 5000] = -32768
-        raw[s, F * nv.FRAME_RAW - 3000:F * nv.FRAME_RAW + 3000] = 32767
-    buf = nv.DeviceBuffer(S * n * 4)
-    buf.upload(raw)
-    with nv.Pipeline(n_streams=S, raw_rate=True, chain_masks=masks, max_frames=F, char_layer=False) as p:
-        refs = []
-        for s in range(S):
-            r = ob.Pipe(chain_mask=masks[s], charlayer=False, tap_y3=(F + F2) * nv.FRAME_Y3)
-            r.push_raw(raw[s])
-            refs.append(r)
-        for f0, k in ((0, F), (F, F2)):
-            p.process_resident(buf, n, f0, k); p.fetch()
-            for s in range(S):
-                for c in range(2):
-                    if (masks[s] >> c) & 1:
-                        want = np.ascontiguousarray(refs[s].y3(c)[f0 * nv.FRAME_Y3:(f0 + k) * nv.FRAME_Y3])
-                        got = p.debug_y3(s, c)
-                        assert got.shape == want.shape and np.array_equal(got.view(np.uint64), want.view(np.uint64)), (masks, s, c, f0)
-                        assert np.abs(want).max() > 10.0
-                        checked += 1
-        for s in range(S):
-            for c in range(2):
-                assert p.bits(s, c) == (refs[s].bits(c) if (masks[s] >> c) & 1 else ""), (masks, s, c)
-    buf.free()
-print("rails ok", checked)
-''')
-    root = str(Path(__file__).resolve().parent.parent)
-    for env in (dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="0"), dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="1"), dict(NVX_INDEPENDENT="1"), {}):
-        out = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
-        assert out.returncode == 0, (env, out.stderr[-3000:])
-        assert out.stdout.strip().splitlines()[-1] == "rails ok 16", env
+    cases = _rails_cases(nv, oracle)
+    for forms in signals.CASCADE_FORMS + (signals.AUTOMATIC,):
+        assert _rails_run(nv, cases, forms) == 16, forms
 
 
-def _run_full_size_total(nv, oracle, S, F, ncpu):
-    """All S streams of a configs[3]-shaped batch against the oracle, bit for bit; returns (checked, bad, seconds, ties)."""
+def _run_full_size_total(nv, oracle, S, F, ncpu, forms=None):
+    """All S streams of a configs[3]-shaped batch against the oracle, bit for bit, in the cascade form `forms` forces (None:
+    the launcher's own choice); returns (checked, bad, seconds, ties)."""
     import fullsize
     pitch = F * nv.FRAME_RAW
     buf = nv.DeviceBuffer(S * pitch * 4)
     streams = [signals.stream_params(nv, s, nv.RATE_RAW)[0] for s in range(S)]
     nv.synth_device(streams, nv.RATE_RAW, pitch, buf, pitch)
-    with nv.Pipeline(n_streams=S, raw_rate=True, chain_mask=nv.CHAIN_518, max_frames=F, char_layer=False) as p:
+    with nv.Pipeline(n_streams=S, raw_rate=True, chain_mask=nv.CHAIN_518, max_frames=F, char_layer=False, forms=forms) as p:
         p.process_resident(buf, pitch, 0, F)
         p.fetch()
+        if forms is not None:
+            signals.assert_cascade_form(p, forms)
         checked, bad, secs = fullsize.verify_streams(oracle, buf, pitch, pitch, True, lambda s: p.bits(s, 0), range(S), ncpu)
         ties = p.tie_stats()
     buf.free()
@@ -426,12 +429,11 @@ import sys, os, json
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
 import navtex_amd as nv, oracle_binding as ob, signals
 import test_gpu_parity as T
-checked, bad, secs, ties = T._run_full_size_total(nv, ob, 4096, 12, int(sys.argv[2]))
+checked, bad, secs, ties = T._run_full_size_total(nv, ob, 4096, 12, int(sys.argv[2]), signals.INDEPENDENT)
 print(json.dumps({"checked": checked, "bad": bad[:20], "n_bad": len(bad), "secs": secs, "ties": ties}))
 ''')
     root = str(Path(__file__).resolve().parent.parent)
-    out = subprocess.run([sys.executable, str(script), root, str(ncpu)], capture_output=True, text=True, timeout=900,
-                         env=dict(os.environ, NVX_INDEPENDENT="1"))
+    out = subprocess.run([sys.executable, str(script), root, str(ncpu)], capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads(out.stdout.strip().splitlines()[-1])
     assert rec["checked"] == S and rec["n_bad"] == 0, rec
@@ -513,42 +515,36 @@ def test_launches_on_different_streams_stay_ordered(nv, oracle):
     buf.free()
 
 
-def test_demodulator_front_forms_agree_bit_for_bit(nv, tmp_path):
+def _front_run(nv, forms):
+    h = hashlib.sha256()
+    masks = [1, 3, 2]
+    streams = [signals.stream_params(nv, 900 + s, nv.RATE_IN, n_phasing=14)[0] for s in range(3)]
+    F = 39
+    buf = nv.DeviceBuffer(3 * F * nv.FRAME_IN * 4)
+    nv.synth_device(streams, nv.RATE_IN, F * nv.FRAME_IN, buf, F * nv.FRAME_IN)
+    with nv.Pipeline(n_streams=3, raw_rate=False, chain_masks=masks, max_frames=25, forms=forms) as p:
+        p.enable_debug(True)
+        f0 = 0
+        for k in (4, 25, 9, 1):
+            p.process_resident(buf, F * nv.FRAME_IN, f0, k); f0 += k
+            p.fetch()
+            signals.assert_front_form(p, forms, tiles_fit=k > 1)
+            for s in range(3):
+                for c in range(2):
+                    if (masks[s] >> c) & 1: h.update(p.debug_dphi(s, c)[: k * nv.FRAME_Y3].tobytes())
+        for s in range(3):
+            for c in range(2): h.update(p.bits(s, c).encode())
+        h.update(repr(sorted(p.messages)).encode()); h.update(repr(p.tie_stats()).encode())
+        nbits = sum(len(p.bits(s, c)) for s in range(3) for c in range(2))
+        n_messages = len(p.messages)
+    buf.free()
+    return h.hexdigest(), nbits, n_messages
+
+
+def test_demodulator_front_forms_agree_bit_for_bit(nv):
     """The demodulator's front has two forms (r3): one workgroup per chain walking the tiles of a launch (many chains), or
     one workgroup per tile from the third tile on, each rebuilding its 577-sample look-back (few chains, long launches;
-    chosen automatically).  Forced either way in a subprocess: delta-phi, bits and messages of launches of 4 + 25 + 9 + 1
+    chosen automatically).  Forced either way: delta-phi, bits and messages of launches of 4 + 25 + 9 + 1
     frames (one to six tiles, carried state in between) are identical, and so are the tie statistics."""
-    import hashlib, subprocess, sys, os
-    script = tmp_path / "run.py"
-    script.write_text('''
-import sys, hashlib
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import numpy as np, navtex_amd as nv, signals
-h = hashlib.sha256()
-masks = [1, 3, 2]
-streams = [signals.stream_params(nv, 900 + s, nv.RATE_IN, n_phasing=14)[0] for s in range(3)]
-F = 39
-buf = nv.DeviceBuffer(3 * F * nv.FRAME_IN * 4)
-nv.synth_device(streams, nv.RATE_IN, F * nv.FRAME_IN, buf, F * nv.FRAME_IN)
-with nv.Pipeline(n_streams=3, raw_rate=False, chain_masks=masks, max_frames=25) as p:
-    p.enable_debug(True)
-    f0 = 0
-    for k in (4, 25, 9, 1):
-        p.process_resident(buf, F * nv.FRAME_IN, f0, k); f0 += k
-        p.fetch()
-        for s in range(3):
-            for c in range(2):
-                if (masks[s] >> c) & 1: h.update(p.debug_dphi(s, c)[: k * nv.FRAME_Y3].tobytes())
-    for s in range(3):
-        for c in range(2): h.update(p.bits(s, c).encode())
-    h.update(repr(sorted(p.messages)).encode()); h.update(repr(p.tie_stats()).encode())
-    nbits = sum(len(p.bits(s, c)) for s in range(3) for c in range(2))
-print(h.hexdigest(), nbits, len(p.messages))
-''')
-    root = str(Path(__file__).resolve().parent.parent)
-    outs = []
-    for force in ("0", "1"):
-        out = subprocess.run([sys.executable, str(script), root], capture_output=True, text=True, timeout=300, env=dict(os.environ, NVX_DEMOD_TILES=force))
-        assert out.returncode == 0, out.stderr[-2000:]
-        outs.append(out.stdout.strip().splitlines()[-1].split())
-    assert outs[0] == outs[1] and int(outs[0][1]) > 4000, outs
+    outs = [_front_run(nv, forms) for forms in (signals.WALK, signals.TILES)]
+    assert outs[0] == outs[1] and outs[0][1] > 4000, outs

@@ -6,12 +6,6 @@ terms' magnitudes, the derived fields the header's formulas of the returned sums
 in both stage-0 forms, push mode with ragged ends (tails below and around g = 8), a wideband handle, both front forms
 (each bit-identical across two runs), bits and messages unchanged by reports, the read / reset / enable semantics, the
 physical checks of tests/test_signal_report.py on decoded streams, the headline scale and a group."""
-import json
-import os
-import subprocess
-import sys
-from pathlib import Path
-
 import numpy as np
 import pytest
 
@@ -20,7 +14,6 @@ import signals
 import timing_ref as tr
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 
 
 def check_reports(oracle, p, taps, reset=False):
@@ -110,52 +103,43 @@ def test_wideband_reports_equal_the_restatement(nv, oracle):
     assert total == 16 * (F * nv.FRAME_Y3 - sr.G_DAB)
 
 
-FORMS_SCRIPT = r'''
-import sys, json
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import numpy as np, navtex_amd as nv, oracle_binding as oracle, signals, timing_ref as tr
-from test_gpu_signal_report import check_reports
-masks = [1, 3, 2]
-streams = [signals.stream_params(nv, 950 + s, nv.RATE_IN, n_phasing=14)[0] for s in range(3)]
-F = 39
-buf = nv.DeviceBuffer(3 * F * nv.FRAME_IN * 4)
-nv.synth_device(streams, nv.RATE_IN, F * nv.FRAME_IN, buf, F * nv.FRAME_IN)
-with nv.Pipeline(n_streams=3, raw_rate=False, chain_masks=masks, max_frames=25) as p:
-    p.enable_debug(True)
-    p.enable_signal_report(True)
-    chains = [(s, c) for s in range(3) for c in range(2) if (masks[s] >> c) & 1]
-    taps = tr.DeviceTaps(p, chains, push_mode=False)
-    f0 = 0
-    for k in (1, 4, 25, 9):
-        taps.launch(lambda: p.process_resident(buf, F * nv.FRAME_IN, f0, k)); f0 += k
-    total = check_reports(oracle, p, taps)
-    reps = {f"{s}/{c}": {k: float(v).hex() if isinstance(v, float) else v for k, v in p.signal_report(s, c).items()} for s, c in chains}
-buf.free()
-print("RESULT", total, json.dumps(reps))
-'''
+def _front_form_reports(nv, oracle, buf, F, forms):
+    """(samples reported, {chain: report with its floats as hex}) of launches of 1, 4, 25 and 9 frames in the front form `forms` forces"""
+    masks = [1, 3, 2]
+    with nv.Pipeline(n_streams=3, raw_rate=False, chain_masks=masks, max_frames=25, forms=forms) as p:
+        p.enable_debug(True)
+        p.enable_signal_report(True)
+        chains = [(s, c) for s in range(3) for c in range(2) if (masks[s] >> c) & 1]
+        taps = tr.DeviceTaps(p, chains, push_mode=False)
+        f0 = 0
+        for k in (1, 4, 25, 9):
+            taps.launch(lambda: p.process_resident(buf, F * nv.FRAME_IN, f0, k)); f0 += k
+            signals.assert_front_form(p, forms, tiles_fit=k > 1)
+        total = check_reports(oracle, p, taps)
+        reps = {f"{s}/{c}": {k: float(v).hex() if isinstance(v, float) else v for k, v in p.signal_report(s, c).items()} for s, c in chains}
+    return total, reps
 
 
-def test_both_front_forms_equal_the_restatement_and_repeat_bit_for_bit(nv, tmp_path):
-    """The walk (NVX_DEMOD_TILES=0) and head + tiles (=1), each twice in fresh processes: launches of 1, 4, 25 and 9 frames
-    (under =1 three of them take the tile form).  Each run equals the restatement; the two runs of a form agree in every
-    bit of every field."""
-    script = tmp_path / "forms.py"
-    script.write_text(FORMS_SCRIPT)
+def test_both_front_forms_equal_the_restatement_and_repeat_bit_for_bit(nv, oracle):
+    """The walk and head + tiles, each forced, twice: launches of 1, 4, 25 and 9 frames
+    (with tiles forced three of them take the tile form).  Each run equals the restatement; the two runs of a form agree in
+    every bit of every field."""
+    streams = [signals.stream_params(nv, 950 + s, nv.RATE_IN, n_phasing=14)[0] for s in range(3)]
+    F = 39
+    buf = nv.DeviceBuffer(3 * F * nv.FRAME_IN * 4)
+    nv.synth_device(streams, nv.RATE_IN, F * nv.FRAME_IN, buf, F * nv.FRAME_IN)
     seen = {}
-    for force in ("0", "1"):
+    for forms in (signals.WALK, signals.TILES):
         runs = []
         for _ in range(2):
-            out = subprocess.run([sys.executable, str(script), str(ROOT)], capture_output=True, text=True, timeout=300,
-                                 env=dict(os.environ, NVX_DEMOD_TILES=force))
-            assert out.returncode == 0, out.stderr[-3000:]
-            line = [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1]
-            total, reps = line.split(" ", 2)[1:]
-            assert int(total) == 4 * (39 * 288 - 8)
-            runs.append(json.loads(reps))
-        assert runs[0] == runs[1], f"NVX_DEMOD_TILES={force}: two runs differ"
-        seen[force] = runs[0]
-    for k in seen["0"]:                                     # the forms count the same samples (their sums may differ in the last bits)
-        assert seen["0"][k]["samples"] == seen["1"][k]["samples"] and seen["0"][k]["b_samples"] == seen["1"][k]["b_samples"]
+            total, reps = _front_form_reports(nv, oracle, buf, F, forms)
+            assert total == 4 * (39 * 288 - 8)
+            runs.append(reps)
+        assert runs[0] == runs[1], f"forms {forms}: two runs differ"
+        seen[forms] = runs[0]
+    buf.free()
+    for k in seen[signals.WALK]:                            # the forms count the same samples (their sums may differ in the last bits)
+        assert seen[signals.WALK][k]["samples"] == seen[signals.TILES][k]["samples"] and seen[signals.WALK][k]["b_samples"] == seen[signals.TILES][k]["b_samples"]
 
 
 def test_reports_change_no_bit_and_no_message(nv, oracle):

@@ -7,10 +7,6 @@ by the mode.  Covered: resident and list launches, a ragged end, raw rate in bot
 wideband handle, both forms of the front, chains spread over several FSM workgroups, the mode's semantics, and the
 acceptance case end to end (tests/test_soft.py) through one handle."""
 import ctypes as C
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -19,7 +15,6 @@ import signals
 import soft_ref
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 
 
 class Collector:
@@ -158,39 +153,25 @@ def test_other_configurations(nv, oracle, name):
     _config_case(nv, oracle, name)
 
 
-FORMS_SCRIPT = r'''
-import sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import numpy as np, navtex_amd as nv, oracle_binding as oracle, signals
-from test_gpu_soft import Collector, check_values
-F = 12
-st = signals.stream_params(nv, 4300, nv.RATE_IN, noise_amp=4000)[0]
-buf = nv.DeviceBuffer(2 * F * nv.FRAME_IN * 4)
-nv.synth_device([st], nv.RATE_IN, 2 * F * nv.FRAME_IN, buf, 2 * F * nv.FRAME_IN)
-with nv.Pipeline(n_streams=1, chain_mask=3, max_frames=F, char_layer=False) as p:
-    p.enable_soft(3)
-    col = Collector(p, 1, False)
-    for f0 in (0, F):                     # 12 frames = 8 tiles: head + 6 tile workgroups when the tile form is taken
-        col.step(lambda: p.process_resident(buf, 2 * F * nv.FRAME_IN, f0, F), [0])
-    got = check_values(nv, oracle, p, col, [(0, 0), (0, 1)])
-buf.free()
-print("RESULT", sum(len(b) for b, _ in got.values()), " ".join(v.tobytes().hex() for _, v in got.values()))
-'''
-
-
-def test_both_forms_of_the_front_give_the_same_values(nv, tmp_path):
-    """One stream x 12 frames, twice, with the walk (NVX_DEMOD_TILES=0) and with head + tiles (=1), in fresh processes: each
+def test_both_forms_of_the_front_give_the_same_values(nv, oracle):
+    """One stream x 12 frames, twice, with the walk and with head + tiles forced: each
     equals the restatement, and the two agree in every bit."""
-    script = tmp_path / "forms.py"
-    script.write_text(FORMS_SCRIPT)
+    F = 12
+    st = signals.stream_params(nv, 4300, nv.RATE_IN, noise_amp=4000)[0]
+    buf = nv.DeviceBuffer(2 * F * nv.FRAME_IN * 4)
+    nv.synth_device([st], nv.RATE_IN, 2 * F * nv.FRAME_IN, buf, 2 * F * nv.FRAME_IN)
     seen = []
-    for force in ("0", "1"):
-        out = subprocess.run([sys.executable, str(script), str(ROOT)], capture_output=True, text=True, timeout=300,
-                             env=dict(os.environ, NVX_DEMOD_TILES=force))
-        assert out.returncode == 0, out.stderr[-3000:]
-        line = [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split(" ", 2)
-        assert int(line[1]) > 2 * 20 * 32                 # (two chains, 24 frames of 32 bits less the timing filter's priming)
-        seen.append(line[2])
+    for forms in (signals.WALK, signals.TILES):
+        with nv.Pipeline(n_streams=1, chain_mask=3, max_frames=F, char_layer=False, forms=forms) as p:
+            p.enable_soft(3)
+            col = Collector(p, 1, False)
+            for f0 in (0, F):                     # 12 frames = 8 tiles: head + 6 tile workgroups when the tile form is taken
+                col.step(lambda: p.process_resident(buf, 2 * F * nv.FRAME_IN, f0, F), [0])
+                assert p.last_forms()[2] == (6 if forms == signals.TILES else 0)
+            got = check_values(nv, oracle, p, col, [(0, 0), (0, 1)])
+        assert sum(len(b) for b, _ in got.values()) > 2 * 20 * 32      # (two chains, 24 frames of 32 bits less the timing filter's priming)
+        seen.append(" ".join(v.tobytes().hex() for _, v in got.values()))
+    buf.free()
     assert seen[0] == seen[1]
 
 

@@ -12,9 +12,6 @@ every run, over all its launches, the oracle is fed that chain's own 900 S/s sam
 and nvx_demod_tie_stats must report what the oracle's class sums give.  tests/test_timing_filter.py pins the oracle's
 taps to the compiled reference and to a restatement of decoder.C on CPU."""
 import ctypes as C
-import os
-import subprocess
-import sys
 from pathlib import Path
 
 import numpy as np
@@ -66,48 +63,34 @@ def check_chains(nv, oracle, taps, p=None, cover=None):
     return n_chains, n_samples
 
 
-FORMS_SCRIPT = r'''
-import sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import numpy as np, navtex_amd as nv, oracle_binding as oracle, signals, timing_ref as tr
-from test_gpu_timing_filter import check_chains
-masks = [1, 3, 2]
-streams = [signals.stream_params(nv, 900 + s, nv.RATE_IN, n_phasing=14)[0] for s in range(3)]
-F = 39
-buf = nv.DeviceBuffer(3 * F * nv.FRAME_IN * 4)
-nv.synth_device(streams, nv.RATE_IN, F * nv.FRAME_IN, buf, F * nv.FRAME_IN)
-cover = set()
-with nv.Pipeline(n_streams=3, raw_rate=False, chain_masks=masks, max_frames=25) as p:
-    p.enable_debug(True)
-    taps = tr.DeviceTaps(p, [(s, c) for s in range(3) for c in range(2) if (masks[s] >> c) & 1], push_mode=False)
-    f0 = 0
-    for k in (1, 4, 25, 9):
-        taps.launch(lambda: p.process_resident(buf, F * nv.FRAME_IN, f0, k)); f0 += k
-    chains, samples = check_chains(nv, oracle, taps, p, cover)
-buf.free()
-print("RESULT", chains, samples, len(cover), taps.n_launches)
-'''
-
-
-def test_both_front_forms_equal_the_oracle_at_every_stage(nv, tmp_path):
-    """The walk (NVX_DEMOD_TILES=0) and head + tiles (=1), each in a fresh process: launches of 1, 4, 25 and 9 frames of three
-    streams (four chains) carry the state from launch to launch; under =1 the launches of 4, 25 and 9 frames have 3, 17
-    and 6 tiles and take the tile form (launcher rule: tiles >= 3), each tile storing only its own samples.  Every stage
-    equals the oracle, and S is compared at every residue g mod 5103 (the ring algebra's whole period)."""
-    script = tmp_path / "forms.py"
-    script.write_text(FORMS_SCRIPT)
-    tiles = [(k * 288 + 431) // 432 for k in (1, 4, 25, 9)]
-    for force in ("0", "1"):
-        ran_tiles = sum(1 for t in tiles if t >= 3 and force == "1")
-        assert ran_tiles == (3 if force == "1" else 0)
-        out = subprocess.run([sys.executable, str(script), str(ROOT)], capture_output=True, text=True, timeout=300,
-                             env=dict(os.environ, NVX_DEMOD_TILES=force))
-        assert out.returncode == 0, out.stderr[-3000:]
-        res = [l for l in out.stdout.splitlines() if l.startswith("RESULT")][-1].split()
-        chains, samples, cover, launches = map(int, res[1:])
-        print(f"NVX_DEMOD_TILES={force}: {chains} chains, {samples} samples, {launches} launches ({ran_tiles} in the tile form), "
-              f"{cover} residues mod 5103")
-        assert chains == 4 and samples == 4 * 39 * 288 and launches == 4 and cover == tr.MOD
+def test_both_front_forms_equal_the_oracle_at_every_stage(nv, oracle):
+    """The walk and head + tiles, each forced: launches of 1, 4, 25 and 9 frames of three
+    streams (four chains) carry the state from launch to launch; with tiles forced the launches of 4, 25 and 9 frames have
+    3, 17 and 6 tiles and take the tile form (launcher rule: tiles >= 3; the handle reports what ran), each tile storing
+    only its own samples.  Every stage equals the oracle, and S is compared at every residue g mod 5103 (the ring algebra's
+    whole period)."""
+    masks = [1, 3, 2]
+    streams = [signals.stream_params(nv, 900 + s, nv.RATE_IN, n_phasing=14)[0] for s in range(3)]
+    F = 39
+    buf = nv.DeviceBuffer(3 * F * nv.FRAME_IN * 4)
+    nv.synth_device(streams, nv.RATE_IN, F * nv.FRAME_IN, buf, F * nv.FRAME_IN)
+    for forms in (signals.WALK, signals.TILES):
+        cover = set()
+        ran_tiles = 0
+        with nv.Pipeline(n_streams=3, raw_rate=False, chain_masks=masks, max_frames=25, forms=forms) as p:
+            p.enable_debug(True)
+            taps = tr.DeviceTaps(p, [(s, c) for s in range(3) for c in range(2) if (masks[s] >> c) & 1], push_mode=False)
+            f0 = 0
+            for k in (1, 4, 25, 9):
+                taps.launch(lambda: p.process_resident(buf, F * nv.FRAME_IN, f0, k)); f0 += k
+                signals.assert_front_form(p, forms, tiles_fit=k > 1)
+                ran_tiles += p.last_forms()[2] > 0
+            chains, samples = check_chains(nv, oracle, taps, p, cover)
+        assert ran_tiles == (3 if forms == signals.TILES else 0)
+        print(f"forms {forms}: {chains} chains, {samples} samples, {taps.n_launches} launches ({ran_tiles} in the tile form), "
+              f"{len(cover)} residues mod 5103")
+        assert chains == 4 and samples == 4 * 39 * 288 and taps.n_launches == 4 and len(cover) == tr.MOD
+    buf.free()
 
 
 # (900 S/s samples of the stream, as whole frames F + the rest r): priming thresholds 8 / 574 / 582 and the ninth sample

@@ -2,11 +2,8 @@
 bit-identical to the restatement (tests/tune_ref.py) in every kernel form, nominal chains bit-identical to an untuned
 handle's, messages on carriers the reference mixer cannot decode, retuning at a frame boundary, scale, groups, errors
 and signal reports against the tuned carrier."""
-import os
-import subprocess
-import sys
+import hashlib
 from concurrent.futures import ThreadPoolExecutor
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -16,7 +13,6 @@ import signals
 import tune_ref as tr
 
 pytestmark = pytest.mark.gpu
-ROOT = Path(__file__).resolve().parent.parent
 
 
 def _u64(a):
@@ -35,8 +31,9 @@ CASE2 = ([3, 3, 1], {(0, 0): 3000.0, (0, 1): -9000.0, (1, 1): 4481 * 3.125, (2, 
 CASE1 = ([1, 2, 1], {(0, 0): -9000.0, (1, 1): 4481 * 3.125, (2, 0): 19000.0})
 
 
-def _run(nv, raw, s0, masks, tune, frames=3, launches=(3,)):
-    """Launch a handle over streams 500.. with `tune` applied; returns (y3 per launch per slot, bits per slot, iqs)."""
+def _run(nv, raw, s0, masks, tune, frames=3, launches=(3,), forms=None):
+    """Launch a handle over streams 500.. with `tune` applied, in the cascade form `forms` forces (None: the launcher's own);
+    returns (y3 per launch per slot, bits per slot, iqs)."""
     rate = nv.RATE_RAW if raw else nv.RATE_IN
     frame = nv.FRAME_RAW if raw else nv.FRAME_IN
     n = len(masks)
@@ -46,13 +43,15 @@ def _run(nv, raw, s0, masks, tune, frames=3, launches=(3,)):
     for s in range(n):
         buf.upload(iqs[s], s * pitch * 4)
     y3s, bits = {}, {}
-    with nv.Pipeline(n_streams=n, raw_rate=raw, chain_masks=masks, max_frames=max(launches), char_layer=False, stage0_order=s0) as p:
+    with nv.Pipeline(n_streams=n, raw_rate=raw, chain_masks=masks, max_frames=max(launches), char_layer=False, stage0_order=s0, forms=forms) as p:
         for (s, c), hz in tune.items():
             assert p.set_carrier(s, c, hz) == tr.k_of(hz) * 3.125
         f0 = 0
         for nf in launches:
             p.process_resident(buf, pitch, f0, nf)
             p.fetch()
+            if forms is not None:
+                signals.assert_cascade_form(p, forms)
             for s in range(n):
                 for c in range(2):
                     if (masks[s] >> c) & 1:
@@ -85,25 +84,16 @@ def test_tuned_chains_are_bit_identical_to_the_restatement(nv, raw, s0, case):
         assert np.array_equal(_u64(y3s[(1, 0)]), _u64(y3u[(1, 0)])) and bits[(1, 0)] == bitsu[(1, 0)]
 
 
-def test_unit_forms_agree_with_the_restatement(nv, tmp_path):
-    """The hand-over forms (waiting, pre-rolling) and independent units, forced in child processes: y3 and bits of 7 + 3
+def test_unit_forms_agree_with_the_restatement(nv):
+    """The hand-over forms (waiting, pre-rolling) and independent units, each forced: y3 and bits of 7 + 3
     frames with tuned chains, as digests, equal among themselves and to the restatement's."""
-    script = tmp_path / "run.py"
-    script.write_text('''
-import sys, hashlib
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import numpy as np, navtex_amd as nv, test_gpu_tune as t
-h = hashlib.sha256()
-for raw in (False, True):
-    y3s, bits, _ = t._run(nv, raw, 1, [3, 1, 3], {(0, 0): 3000.0, (0, 1): -9000.0, (2, 1): 4481 * 3.125, (1, 0): 150.0}, frames=10, launches=(7, 3))
-    for k in sorted(y3s): h.update(y3s[k].tobytes()); h.update(bits[k].encode())
-print(h.hexdigest())
-''')
     digests = []
-    for env in (dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="0"), dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="1"), dict(NVX_INDEPENDENT="1")):
-        out = subprocess.run([sys.executable, str(script), str(ROOT)], capture_output=True, text=True, timeout=300, env=dict(os.environ, **env))
-        assert out.returncode == 0, out.stderr[-2000:]
-        digests.append(out.stdout.strip().splitlines()[-1])
+    for forms in signals.CASCADE_FORMS:
+        h = hashlib.sha256()
+        for raw in (False, True):
+            y3s, bits, _ = _run(nv, raw, 1, [3, 1, 3], {(0, 0): 3000.0, (0, 1): -9000.0, (2, 1): 4481 * 3.125, (1, 0): 150.0}, frames=10, launches=(7, 3), forms=forms)
+            for k in sorted(y3s): h.update(y3s[k].tobytes()); h.update(bits[k].encode())
+        digests.append(h.hexdigest())
     assert digests[0] == digests[1] == digests[2] and len(digests[0]) == 64
     # and one of them against the restatement (the 252 kS/s run)
     tune = {(0, 0): 3000.0, (0, 1): -9000.0, (2, 1): 4481 * 3.125, (1, 0): 150.0}

@@ -28,9 +28,10 @@ import tune_ref as tr
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 
-# the unit forms: the launcher's own choice / hand-over where a unit whose predecessor is still running waits for it /
-# hand-over where such a unit pre-rolls instead (its first FIR1 output index goes back behind the frame start)
-FORMS = ({}, dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="0"), dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="1"))
+# the unit forms (Pipeline(forms=...)): the launcher's own choice / hand-over where a unit whose predecessor is still
+# running waits for it / hand-over where such a unit pre-rolls instead (its first FIR1 output index goes back behind the
+# frame start)
+FORMS = (None, signals.HANDOVER_WAITING, signals.HANDOVER_PREROLLING)
 
 
 def two_carrier_stream(nv, sid, rate):
@@ -64,13 +65,15 @@ def _popcount(masks):
     return int(sum(bin(int(m)).count("1") for m in masks))
 
 
-def _launches(nv, p, buf, pitch, plan, taps=()):
+def _launches(nv, p, buf, pitch, plan, taps=(), forms=None):
     """Launch `plan` (frames per launch) from frame 0; with taps [(stream, chain)] every launch is fetched and their y3
-    collected: returns {(s, c): y3 of all launches}."""
+    collected: returns {(s, c): y3 of all launches}.  forms: what the handle was made with -- every launch took it."""
     got = {key: [] for key in taps}
     f0 = 0
     for k in plan:
         p.process_resident(buf, pitch, f0, k); f0 += k
+        if forms is not None:
+            signals.assert_cascade_form(p, forms)
         if taps:
             p.fetch()
             for key in taps:
@@ -114,7 +117,7 @@ def _verdict(p, ob, buf, pitch, masks, raw, bits, ncpu):
 
 
 # ------------------------------------------------------------------------------------------------ the runs (parent or child)
-def run_raw_total(nv, ob, S=4096, F=12, ncpu=16, extras=True, buf=None):
+def run_raw_total(nv, ob, S=4096, F=12, ncpu=16, extras=True, buf=None, forms=None):
     """Test 1: S two-carrier streams x F frames at the raw rate, chain_mask 3, one launch.  extras: the y3 spread, the 5 + 7
     partition and the run with signal reports on.  buf: the input buffer of S * F * FRAME_RAW * 4 bytes, allocated by the
     caller (who alone decides what a failed allocation means) or, in a child process, here; it is freed here either way."""
@@ -124,8 +127,8 @@ def run_raw_total(nv, ob, S=4096, F=12, ncpu=16, extras=True, buf=None):
     try:
         nv.synth_device([two_carrier_stream(nv, s, nv.RATE_RAW) for s in range(S)], nv.RATE_RAW, pitch, buf, pitch)
         masks = [3] * S
-        with nv.Pipeline(n_streams=S, raw_rate=True, chain_mask=3, max_frames=F, char_layer=False) as p:
-            y3 = _launches(nv, p, buf, pitch, [F], _spread_taps(S, masks) if extras else ())
+        with nv.Pipeline(n_streams=S, raw_rate=True, chain_mask=3, max_frames=F, char_layer=False, forms=forms) as p:
+            y3 = _launches(nv, p, buf, pitch, [F], _spread_taps(S, masks) if extras else (), forms)
             bits = _all_bits(p, S)
             rec = _verdict(p, ob, buf, pitch, masks, True, bits, ncpu)
             if extras:
@@ -153,15 +156,15 @@ def mixed_masks(S):
     return [int(m) for m in np.random.default_rng(41).choice([1, 2, 3], size=S, p=[.25, .25, .5])]
 
 
-def run_252k_mixed(nv, ob, S=4096, F=12, ncpu=16, extras=True):
+def run_252k_mixed(nv, ob, S=4096, F=12, ncpu=16, extras=True, forms=None):
     """Test 2: S two-carrier streams x F frames at 252 kS/s, masks 1 / 2 / 3 mixed, launches of 5 + 7."""
     pitch = F * nv.FRAME_IN
     masks = mixed_masks(S)
     buf = nv.DeviceBuffer(S * pitch * 4)
     try:
         nv.synth_device([two_carrier_stream(nv, s, nv.RATE_IN) for s in range(S)], nv.RATE_IN, pitch, buf, pitch)
-        with nv.Pipeline(n_streams=S, raw_rate=False, chain_masks=masks, max_frames=7, char_layer=False) as p:
-            y3 = _launches(nv, p, buf, pitch, [5, 7], _spread_taps(S, masks) if extras else ())
+        with nv.Pipeline(n_streams=S, raw_rate=False, chain_masks=masks, max_frames=7, char_layer=False, forms=forms) as p:
+            y3 = _launches(nv, p, buf, pitch, [5, 7], _spread_taps(S, masks) if extras else (), forms)
             bits = _all_bits(p, S)
             rec = _verdict(p, ob, buf, pitch, masks, False, bits, ncpu)
             if extras:
@@ -171,7 +174,7 @@ def run_252k_mixed(nv, ob, S=4096, F=12, ncpu=16, extras=True):
     return rec
 
 
-def run_cic3_hand_over(nv, ob, S=3000, ncpu=16):
+def run_cic3_hand_over(nv, ob, S=3000, ncpu=16, forms=None):
     """Test 3: S two-carrier streams x 3 frames at the raw rate through the third-order stage 0, launches of 2 + 1."""
     F = 3
     pitch = F * nv.FRAME_RAW
@@ -179,8 +182,8 @@ def run_cic3_hand_over(nv, ob, S=3000, ncpu=16):
     buf = nv.DeviceBuffer(S * pitch * 4)
     try:
         nv.synth_device([two_carrier_stream(nv, s, nv.RATE_RAW) for s in range(S)], nv.RATE_RAW, pitch, buf, pitch)
-        with nv.Pipeline(n_streams=S, raw_rate=True, chain_mask=3, max_frames=2, char_layer=False, stage0_order=3) as p:
-            _launches(nv, p, buf, pitch, [2, 1])
+        with nv.Pipeline(n_streams=S, raw_rate=True, chain_mask=3, max_frames=2, char_layer=False, stage0_order=3, forms=forms) as p:
+            _launches(nv, p, buf, pitch, [2, 1], forms=forms)
             rec = _verdict(p, ob, buf, pitch, masks, 3, _all_bits(p, S), ncpu)
     finally:
         buf.free()
@@ -214,7 +217,7 @@ def _digest(y3, bits):
     return hashlib.sha256(np.ascontiguousarray(y3, dtype=np.float64).tobytes() + bits.encode()).hexdigest()
 
 
-def run_tuned(nv, ob, kind, out_path, untuned=False, S=TUNED_S):
+def run_tuned(nv, ob, kind, out_path, untuned=False, S=TUNED_S, forms=None):
     """One child of test 4: the tuned handle over S streams x 3 frames in launches of 2 + 1; one digest per chain over its y3 of
     both launches and its bits, written to out_path as JSON.  untuned: the same batch through an untuned handle too, and the
     digests of the chains left at their nominal k from it."""
@@ -228,11 +231,11 @@ def run_tuned(nv, ob, kind, out_path, untuned=False, S=TUNED_S):
     try:
         nv.synth_device(_tuned_streams(nv, rate, S), rate, pitch, buf, pitch)
         for tuned in ((True, False) if untuned else (True,)):
-            with nv.Pipeline(n_streams=S, raw_rate=raw, chain_mask=3, max_frames=max(TUNED_PLAN), char_layer=False, stage0_order=order) as p:
+            with nv.Pipeline(n_streams=S, raw_rate=raw, chain_mask=3, max_frames=max(TUNED_PLAN), char_layer=False, stage0_order=order, forms=forms) as p:
                 if tuned:
                     rec["carrier_bad"] = [(s, c) for s, c in chains if not left[s, c] and p.set_carrier(s, c, int(ks[s, c]) * 3.125) != int(ks[s, c]) * 3.125][:20]
                     rec["carriers_set"] = int((~left).sum())
-                y3 = _launches(nv, p, buf, pitch, TUNED_PLAN, chains)
+                y3 = _launches(nv, p, buf, pitch, TUNED_PLAN, chains, forms)
                 dig = {f"{s},{c}": _digest(y3[(s, c)], p.bits(s, c)) for s, c in chains if tuned or left[s, c]}
                 rec["digests" if tuned else "untuned_digests"] = dig
                 rec["seals" if tuned else "untuned_seals"] = list(p.integrity_stats()[:2])
@@ -272,16 +275,16 @@ print(json.dumps(getattr(T, sys.argv[2])(nv, ob, **json.loads(sys.argv[3]))))
 '''
 
 
-def _child(tmp_path, func, kwargs, env, timeout):
-    """func(nv, oracle, **kwargs) of this module in a fresh process with `env` added; its last stdout line is its JSON answer."""
+def _child(tmp_path, func, kwargs, forms, timeout):
+    """func(nv, oracle, forms=forms, **kwargs) of this module in a fresh process (a second batch of this size needs an address
+    space of its own); the child asserts that its launches took `forms`; its last stdout line is its JSON answer."""
     script = tmp_path / "child.py"
     script.write_text(CHILD)
     t0 = time.perf_counter()
-    out = subprocess.run([sys.executable, str(script), str(ROOT), func, json.dumps(kwargs)], capture_output=True, text=True, timeout=timeout,
-                         env=dict(os.environ, **env))
-    assert out.returncode == 0, (env, out.stderr[-3000:])
+    out = subprocess.run([sys.executable, str(script), str(ROOT), func, json.dumps(dict(kwargs, forms=forms))], capture_output=True, text=True, timeout=timeout)
+    assert out.returncode == 0, (forms, out.stderr[-3000:])
     rec = json.loads(out.stdout.strip().splitlines()[-1])
-    print(f"{func} {kwargs} {env}: {rec} ({time.perf_counter() - t0:.0f} s)")
+    print(f"{func} {kwargs} {forms}: {rec} ({time.perf_counter() - t0:.0f} s)")
     return rec
 
 
@@ -304,7 +307,7 @@ def test_full_size_two_chain_total_parity_raw_rate(nv, oracle, tmp_path):
     assert rec["y3_bad"] == [] and rec["y3_checked"] == 2 * len(fullsize.spread(S, 64)) == 128
     assert rec["partition_differs"] == [] and rec["partition_compared"] == 2 * S       # the library against itself: beside the oracle, never instead
     assert rec["report_differs"] == [] and rec["report_samples_wrong"] == 0 and rec["report_chains"] == 2 * S
-    child = _child(tmp_path, "run_raw_total", dict(S=S, F=F, ncpu=_ncpu(), extras=False), dict(NVX_INDEPENDENT="1"), 900)
+    child = _child(tmp_path, "run_raw_total", dict(S=S, F=F, ncpu=_ncpu(), extras=False), signals.INDEPENDENT, 900)
     assert child["indistinct"] == [] and child["n_bad"] == 0 and child["checked"] == 2 * S, child
     assert child["ties"][0] == 0 and child["ties"][1] > 2 * S * 250 and child["ties"][2] > 2.0 ** -40 and child["seals"] == [0, 0]
 
@@ -324,7 +327,7 @@ def test_two_chain_at_scale_252k_mixed_masks(nv, oracle, tmp_path):
     assert near == 0 and evals > chains * 250 and margin > 2.0 ** -40
     assert rec["seals"] == [0, 0] and rec["launches"] == 2
     assert rec["y3_bad"] == [] and rec["y3_checked"] == _popcount([masks[s] for s in fullsize.spread(S, 64)])
-    child = _child(tmp_path, "run_252k_mixed", dict(S=S, F=F, ncpu=_ncpu(), extras=False), dict(NVX_INDEPENDENT="1"), 900)
+    child = _child(tmp_path, "run_252k_mixed", dict(S=S, F=F, ncpu=_ncpu(), extras=False), signals.INDEPENDENT, 900)
     assert child["indistinct"] == [] and child["n_bad"] == 0 and child["checked"] == chains, child
     assert child["ties"][0] == 0 and child["ties"][1] > chains * 250 and child["ties"][2] > 2.0 ** -40 and child["seals"] == [0, 0]
 
@@ -333,14 +336,14 @@ def test_third_order_two_chain_hand_over_across_launches(nv, tmp_path):
     """3000 streams x 3 frames through nvx_fir_cascade_cic3_2 in launches of 2 + 1, in the launcher's own form, with waiting
     units and with pre-rolling units: all 6000 chains == the oracle (third-order stage 0) in each."""
     S = 3000
-    for env in FORMS:
-        rec = _child(tmp_path, "run_cic3_hand_over", dict(S=S, ncpu=_ncpu()), env, 600)
-        assert rec["indistinct"] == [] and rec["n_bad"] == 0 and rec["checked"] == 2 * S, (env, rec)
-        assert rec["launches"] == 2 and rec["seals"] == [0, 0], (env, rec)
+    for forms in FORMS:
+        rec = _child(tmp_path, "run_cic3_hand_over", dict(S=S, ncpu=_ncpu()), forms, 600)
+        assert rec["indistinct"] == [] and rec["n_bad"] == 0 and rec["checked"] == 2 * S, (forms, rec)
+        assert rec["launches"] == 2 and rec["seals"] == [0, 0], (forms, rec)
         # 3 frames are 864 samples at 900 S/s; a chain's bit-timing window is primed after 574 of them and is evaluated once
         # per bit period of 9 from there: 32 evaluations per chain, of which 25 are asked for; the margin as at full size
         near, evals, margin = rec["ties"]
-        assert near == 0 and evals > 2 * S * 25 and margin > 2.0 ** -40, (env, rec["ties"])
+        assert near == 0 and evals > 2 * S * 25 and margin > 2.0 ** -40, (forms, rec["ties"])
 
 
 @pytest.mark.parametrize("kind", list(KINDS))
@@ -358,15 +361,15 @@ def test_tuned_chains_in_the_many_streams_form(nv, kind, tmp_path):
     print(f"restatement of {len(want)} chains: {time.perf_counter() - t0:.0f} s")
     # no two chains alike (a swapped pair would show) but the two of stream 4, which run at one k on one input
     assert len(want) == 2 * S and len(set(want.values())) == 2 * S - 1 and want["4,0"] == want["4,1"]
-    for i, env in enumerate(FORMS):
+    for i, forms in enumerate(FORMS):
         out = tmp_path / f"digests{i}.json"
-        _child(tmp_path, "run_tuned", dict(kind=kind, out_path=str(out), untuned=(i == 0), S=S), env, 600)
+        _child(tmp_path, "run_tuned", dict(kind=kind, out_path=str(out), untuned=(i == 0), S=S), forms, 600)
         rec = json.loads(out.read_text())
         got = rec["digests"]
         bad = [key for key in want if got.get(key) != want[key]]
-        assert bad == [] and len(got) == len(want) == 2 * S, (env, len(bad), bad[:20])
-        assert rec["carrier_bad"] == [] and rec["carriers_set"] == 2 * S - n_left, env
-        assert rec["seals"] == [0, 0] and rec["launches"] == 2, (env, rec["seals"])
+        assert bad == [] and len(got) == len(want) == 2 * S, (forms, len(bad), bad[:20])
+        assert rec["carrier_bad"] == [] and rec["carriers_set"] == 2 * S - n_left, forms
+        assert rec["seals"] == [0, 0] and rec["launches"] == 2, (forms, rec["seals"])
         if i == 0:
             un = rec["untuned_digests"]
             nominal = [f"{s},{c}" for s in range(S) for c in range(2) if left[s, c]]

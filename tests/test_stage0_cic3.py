@@ -5,17 +5,12 @@ Build-owned definition (the reference starts at 252 kS/s: receiver/capt_sched.c:
 plus what makes it worth having: its alias rejection at the NAVTEX offsets."""
 import ctypes as C
 import hashlib
-import os
-import subprocess
-import sys
-from pathlib import Path
 
 import numpy as np
 import pytest
 
 import signals
 
-ROOT = Path(__file__).resolve().parent.parent
 W3 = np.convolve(np.convolve(np.ones(8, dtype=np.int64), np.ones(8, dtype=np.int64)), np.ones(8, dtype=np.int64))
 
 
@@ -204,81 +199,70 @@ def test_hand_over_form_more_streams_than_resident_waves(nv, oracle):
     buf.free()
 
 
+def _unit_forms_digest(nv, forms):
+    h = hashlib.sha256()
+    for masks in ([1, 2, 1], [3, 1, 3]):
+        streams = [signals.stream_params(nv, 800 + s, nv.RATE_RAW)[0] for s in range(3)]
+        pitch = 8 * nv.FRAME_RAW
+        buf = nv.DeviceBuffer(3 * pitch * 4)
+        nv.synth_device(streams, nv.RATE_RAW, pitch, buf, pitch)
+        with nv.Pipeline(n_streams=3, raw_rate=True, chain_masks=masks, max_frames=5, char_layer=False, stage0_order=3, forms=forms) as p:
+            p.enable_debug(True)
+            p.process_resident(buf, pitch, 0, 5); p.fetch()
+            signals.assert_cascade_form(p, forms)
+            for s in range(3):
+                for c in range(2):
+                    if (masks[s] >> c) & 1: h.update(p.debug_y3(s, c).tobytes())
+            p.process_resident(buf, pitch, 5, 3); p.fetch()
+            signals.assert_cascade_form(p, forms)
+            for s in range(3):
+                for c in range(2): h.update(p.bits(s, c).encode())
+        buf.free()
+    return h.hexdigest()
+
+
 @pytest.mark.gpu
-def test_both_unit_forms_agree(nv, tmp_path):
-    """Hand-over and independent units (nine-pass pre-roll in front of silence for stage 0's history) forced in a
-    subprocess each: identical 900 S/s output and bits."""
-    script = tmp_path / "run.py"
-    script.write_text('''
-import sys, hashlib
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import numpy as np, navtex_amd as nv, signals
-h = hashlib.sha256()
-for masks in ([1, 2, 1], [3, 1, 3]):
-    streams = [signals.stream_params(nv, 800 + s, nv.RATE_RAW)[0] for s in range(3)]
-    pitch = 8 * nv.FRAME_RAW
-    buf = nv.DeviceBuffer(3 * pitch * 4)
-    nv.synth_device(streams, nv.RATE_RAW, pitch, buf, pitch)
-    with nv.Pipeline(n_streams=3, raw_rate=True, chain_masks=masks, max_frames=5, char_layer=False, stage0_order=3) as p:
-        p.enable_debug(True)
-        p.process_resident(buf, pitch, 0, 5); p.fetch()
-        for s in range(3):
-            for c in range(2):
-                if (masks[s] >> c) & 1: h.update(p.debug_y3(s, c).tobytes())
-        p.process_resident(buf, pitch, 5, 3); p.fetch()
-        for s in range(3):
-            for c in range(2): h.update(p.bits(s, c).encode())
-    buf.free()
-print(h.hexdigest())
-''')
-    digests = []
-    for env in (dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="0"), dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="1"), dict(NVX_INDEPENDENT="1")):
-        out = subprocess.run([sys.executable, str(script), str(ROOT)], capture_output=True, text=True, timeout=300,
-                             env=dict(os.environ, **env))
-        assert out.returncode == 0, out.stderr[-2000:]
-        digests.append(out.stdout.strip().splitlines()[-1])
+def test_both_unit_forms_agree(nv):
+    """Hand-over and independent units (nine-pass pre-roll in front of silence for stage 0's history), each forced:
+    identical 900 S/s output and bits."""
+    digests = [_unit_forms_digest(nv, forms) for forms in signals.CASCADE_FORMS]
     assert digests[0] == digests[1] == digests[2] and len(digests[0]) == 64
 
 
-# The input of the rails test below, and the checks it runs in each unit form (a subprocess each: the form is read once
-# per process).  CIC^3 geometry: a 1-KiB load is 256 raw samples (lane l holds 4l .. 4l+3: the pair 62 / 63 holds the
+# The input of the rails test below, and the checks it runs in each unit form.
+# CIC^3 geometry: a 1-KiB load is 256 raw samples (lane l holds 4l .. 4l+3: the pair 62 / 63 holds the
 # last block, whose C and t cross to the next load by the wave rotation and to the next unit through the state block), a
 # pass 2048, a frame 645 120 (a unit), a third 215 040 (a unit in a launch's last frame or in independent launches), the
 # pre-roll 9 passes = 18 432 in front of a unit that rebuilds its histories.
-_RAILS3 = '''
-import sys
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
-import numpy as np, navtex_amd as nv, oracle_binding as ob
-FR, FY = nv.FRAME_RAW, nv.FRAME_Y3
-LOAD, PRE, THIRD = 256, 9 * 2048, FR // 3
-F, F2 = 4, 2
+LOAD, PRE = 256, 9 * 2048
+RAILS3_F, RAILS3_F2 = 4, 2
 HI, LO = 32767, -32768
 ALT = np.where(np.arange(1 << 16) & 1, HI, LO).astype(np.int16)
-rng = np.random.default_rng(303)
 
 
-def rail(kind, m):
+def _rail(kind, m):
     """m samples of rail kind 0..4: both +full scale, both -full scale, I up / Q down, I down / Q up, alternating (I, Q opposite)."""
     if kind == 4:
         return np.stack([ALT[:m], -1 - ALT[:m]], 1)
     return np.tile(np.array([(HI, HI), (LO, LO), (HI, LO), (LO, HI)][kind], np.int16), (m, 1))
 
 
-def make_input(n, s):
+def _rails3_input(nv, rng, n, s):
+    FR, THIRD = nv.FRAME_RAW, nv.FRAME_RAW // 3
     raw = rng.integers(LO, HI + 1, size=(n, 2), dtype=np.int16)            # full-range uniform noise
     at = 1000 + 977 * s
     for k in range(5):                                                      # long stretches of every kind of rail
-        raw[at + 70000 * k:at + 70000 * k + 50000] = rail(k, 50000)
+        raw[at + 70000 * k:at + 70000 * k + 50000] = _rail(k, 50000)
     # samples 240 .. 271 of 600 consecutive loads: the last block pair of a load (lanes 60 .. 63) and the first of the next,
     # a different kind of rail from load to load, noise in between
     base = (at + 360000) // LOAD * LOAD
     for j in range(600):
-        raw[base + LOAD * j + 240:base + LOAD * j + 272] = rail(j % 5, 32)
+        raw[base + LOAD * j + 240:base + LOAD * j + 272] = _rail(j % 5, 32)
     # a step from one rail to another exactly at every unit boundary (frames, thirds; the launch boundary is one of them)
     # and at the first sample of the pre-roll window in front of each
     for k in range(1, n // THIRD):
         for i, b in enumerate((k * THIRD, k * THIRD - PRE)):
-            raw[b - 600:b] = rail((k + i) % 5, 600); raw[b:b + 600] = rail((k + i + 2) % 5, 600)
+            raw[b - 600:b] = _rail((k + i) % 5, 600); raw[b:b + 600] = _rail((k + i + 2) % 5, 600)
     # the carriers of both chains (+-14 kHz) as full-scale square waves: nothing but rails in the input, and 900 S/s output
     # near the largest the cascade can produce, across a frame boundary and a third-of-frame boundary
     t = np.arange(80000)
@@ -288,12 +272,7 @@ def make_input(n, s):
     return raw
 
 
-def stage0_reaches_the_rails(raw):
-    y0 = ob.stage0_cic3(raw)
-    assert y0.max() == HI and y0.min() == LO, (y0.min(), y0.max())
-
-
-def oracle_pipe(mask, raw, n3):
+def _rails3_oracle_pipe(ob, mask, raw, n3):
     r = ob.Pipe(chain_mask=mask, charlayer=False, tap_y3=n3)
     r.set_stage0(3)
     r.push_raw(raw)
@@ -302,85 +281,105 @@ def oracle_pipe(mask, raw, n3):
     return r
 
 
-def same(got, want, what):
+def _same(got, want, what):
     assert got.shape == want.shape and np.array_equal(got.view(np.uint64), want.view(np.uint64)), (what, got.shape, want.shape)
     assert np.abs(want).max() > 300.0, what                                 # not near-silence: the noise alone gives ~700 per frame
 
 
-checked_resident = 0
-n = (F + F2) * FR
-for masks in ([1, 1, 2], [3, 2, 3]):                                        # the one-chain and the two-chain kernel
-    S = len(masks)
-    raw = np.stack([make_input(n, s) for s in range(S)])
-    stage0_reaches_the_rails(raw[0])
-    refs = [oracle_pipe(masks[s], raw[s], (F + F2) * FY) for s in range(S)]
-    buf = nv.DeviceBuffer(S * n * 4)
-    buf.upload(raw)
-    with nv.Pipeline(n_streams=S, raw_rate=True, chain_masks=masks, max_frames=F, char_layer=False, stage0_order=3) as p:
-        for f0, k in ((0, F), (F, F2)):
-            p.process_resident(buf, n, f0, k); p.fetch()
-            for s in range(S):
-                for c in range(2):
-                    if (masks[s] >> c) & 1:
-                        same(p.debug_y3(s, c), np.ascontiguousarray(refs[s].y3(c)[f0 * FY:(f0 + k) * FY]), (masks, s, c, f0))
-                        checked_resident += 1
-        for s in range(S):
-            for c in range(2):
-                assert p.bits(s, c) == (refs[s].bits(c) if (masks[s] >> c) & 1 else ""), (masks, s, c)
-    buf.free()
-
-# push mode, ragged pushes, streams launched as soon as each has a frame (eager_launch): the streams come apart in time, so
-# the launches name their streams -- the list kernels -- and every launch is held against the oracle right after its push
-checked_push = 0
-n = 4 * FR
-for masks in ([1, 2], [3, 1]):
-    S = len(masks)
-    raw = np.stack([make_input(n, s) for s in range(S)])
-    refs = [oracle_pipe(masks[s], raw[s], 4 * FY) for s in range(S)]
-    with nv.Pipeline(n_streams=S, raw_rate=True, chain_masks=masks, max_frames=2, push_mode=True, eager_launch=True,
-                     char_layer=False, stage0_order=3) as p:
-        pos = [0] * S
-        seen = [[0, 0] for _ in range(S)]                                   # frames checked per (stream, chain)
-        while min(pos) < n:
+def _rails3_cases(nv, ob):
+    """The inputs with the oracle's pipes over them, computed once for every unit form: (masks, samples, pipes) of the
+    resident runs, (masks, samples, pipes, pushes as (stream, samples)) of the push-mode runs."""
+    FR, FY = nv.FRAME_RAW, nv.FRAME_Y3
+    rng = np.random.default_rng(303)
+    resident, pushed = [], []
+    n = (RAILS3_F + RAILS3_F2) * FR
+    for masks in ([1, 1, 2], [3, 2, 3]):                                    # the one-chain and the two-chain kernel
+        raw = np.stack([_rails3_input(nv, rng, n, s) for s in range(len(masks))])
+        y0 = ob.stage0_cic3(raw[0])
+        assert y0.max() == HI and y0.min() == LO, (y0.min(), y0.max())      # stage 0 reaches the rails
+        resident.append((masks, raw, [_rails3_oracle_pipe(ob, m, raw[s], (RAILS3_F + RAILS3_F2) * FY) for s, m in enumerate(masks)]))
+    n = 4 * FR
+    for masks in ([1, 2], [3, 1]):
+        S = len(masks)
+        raw = np.stack([_rails3_input(nv, rng, n, s) for s in range(S)])
+        refs = [_rails3_oracle_pipe(ob, masks[s], raw[s], 4 * FY) for s in range(S)]
+        pos, plan = [0] * S, []
+        while min(pos) < n:                                                 # ragged pushes, the streams in random order
             s = int(rng.integers(0, S)) if max(pos) < n else pos.index(min(pos))
             if pos[s] >= n:
                 continue
             m = int(min(n - pos[s], rng.choice([1, 7, 255, 257, 2047, 2049, 18433, int(rng.integers(1, FR))])))   # < a frame: one launch at most
-            before = [p.stream_stats(t)[1] for t in range(S)]
-            p.push(s, raw[s, pos[s]:pos[s] + m]); pos[s] += m
-            for t in range(S):
-                after = p.stream_stats(t)[1]
-                if after == before[t]:
-                    continue
+            plan.append((s, m)); pos[s] += m
+        pushed.append((masks, raw, refs, plan))
+    return resident, pushed
+
+
+def _rails3_run(nv, cases, forms):
+    FR, FY = nv.FRAME_RAW, nv.FRAME_Y3
+    F, F2 = RAILS3_F, RAILS3_F2
+    resident, pushed = cases
+    checked_resident = 0
+    n = (F + F2) * FR
+    for masks, raw, refs in resident:
+        S = len(masks)
+        buf = nv.DeviceBuffer(S * n * 4)
+        buf.upload(raw)
+        with nv.Pipeline(n_streams=S, raw_rate=True, chain_masks=masks, max_frames=F, char_layer=False, stage0_order=3, forms=forms) as p:
+            for f0, k in ((0, F), (F, F2)):
+                p.process_resident(buf, n, f0, k); p.fetch()
+                signals.assert_cascade_form(p, forms)
+                for s in range(S):
+                    for c in range(2):
+                        if (masks[s] >> c) & 1:
+                            _same(p.debug_y3(s, c), np.ascontiguousarray(refs[s].y3(c)[f0 * FY:(f0 + k) * FY]), (masks, s, c, f0))
+                            checked_resident += 1
+            for s in range(S):
                 for c in range(2):
-                    if (masks[t] >> c) & 1:
-                        same(p.debug_y3(t, c), np.ascontiguousarray(refs[t].y3(c)[before[t] * FY:after * FY]), (masks, t, c, before[t]))
-                        seen[t][c] += after - before[t]
-        p.flush()
-        assert [p.stream_stats(t)[1] for t in range(S)] == [4] * S
-        assert p.stream_stats(0)[2] > 0, "no launch named its streams: the list kernels were not run"
-        for t in range(S):
-            for c in range(2):
-                assert seen[t][c] == (4 if (masks[t] >> c) & 1 else 0), (masks, t, c, seen[t][c])
-                checked_push += seen[t][c]
-                assert p.bits(t, c) == (refs[t].bits(c) if (masks[t] >> c) & 1 else ""), (masks, t, c)
-print("rails ok", checked_resident, checked_push)
-'''
+                    assert p.bits(s, c) == (refs[s].bits(c) if (masks[s] >> c) & 1 else ""), (masks, s, c)
+        buf.free()
+
+    # push mode, ragged pushes, streams launched as soon as each has a frame (eager_launch): the streams come apart in time, so
+    # the launches name their streams -- the list kernels -- and every launch is held against the oracle right after its push
+    checked_push = 0
+    for masks, raw, refs, plan in pushed:
+        S = len(masks)
+        with nv.Pipeline(n_streams=S, raw_rate=True, chain_masks=masks, max_frames=2, push_mode=True, eager_launch=True,
+                         char_layer=False, stage0_order=3, forms=forms) as p:
+            pos = [0] * S
+            seen = [[0, 0] for _ in range(S)]                               # frames checked per (stream, chain)
+            for s, m in plan:
+                before = [p.stream_stats(t)[1] for t in range(S)]
+                p.push(s, raw[s, pos[s]:pos[s] + m]); pos[s] += m
+                for t in range(S):
+                    after = p.stream_stats(t)[1]
+                    if after == before[t]:
+                        continue
+                    signals.assert_cascade_form(p, forms)
+                    for c in range(2):
+                        if (masks[t] >> c) & 1:
+                            _same(p.debug_y3(t, c), np.ascontiguousarray(refs[t].y3(c)[before[t] * FY:after * FY]), (masks, t, c, before[t]))
+                            seen[t][c] += after - before[t]
+            p.flush()
+            assert [p.stream_stats(t)[1] for t in range(S)] == [4] * S
+            assert p.stream_stats(0)[2] > 0, "no launch named its streams: the list kernels were not run"
+            for t in range(S):
+                for c in range(2):
+                    assert seen[t][c] == (4 if (masks[t] >> c) & 1 else 0), (masks, t, c, seen[t][c])
+                    checked_push += seen[t][c]
+                    assert p.bits(t, c) == (refs[t].bits(c) if (masks[t] >> c) & 1 else ""), (masks, t, c)
+    return checked_resident, checked_push
 
 
 @pytest.mark.gpu
-def test_full_scale_rails_through_every_third_order_kernel_and_unit_form(tmp_path):
+def test_full_scale_rails_through_every_third_order_kernel_and_unit_form(nv, oracle):
     """The third-order stage 0 at the int16 rails, every one of its four kernels, in every unit form, against the oracle:
     full-range noise with long stretches of each kind of rail; rails over samples 240 .. 271 of 600 consecutive loads
     (the lane pair 62 / 63 whose C and t the wave rotation and the state block carry on); a step from one rail to another
     exactly at every frame, third-of-frame and launch boundary and at the first sample of every pre-roll window.  Resident
     input through the one- and two-chain kernels (two launches), and host input in ragged pushes through the list kernels:
     every launch's 900 S/s output as fp64 bit patterns and the bits == oracle stage 0 -> oracle cascade.  Waiting and
-    pre-rolling hand-over, independent units, and the launcher's own choice, a subprocess each."""
-    script = tmp_path / "rails3.py"
-    script.write_text(_RAILS3)
-    for env in (dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="0"), dict(NVX_INDEPENDENT="0", NVX_DYNAMIC_PREROLL="1"), dict(NVX_INDEPENDENT="1"), {}):
-        out = subprocess.run([sys.executable, str(script), str(ROOT)], capture_output=True, text=True, timeout=600, env=dict(os.environ, **env))
-        assert out.returncode == 0, (env, out.stderr[-3000:])
+    pre-rolling hand-over, independent units, and the launcher's own choice."""
+    cases = _rails3_cases(nv, oracle)
+    for forms in signals.CASCADE_FORMS + (signals.AUTOMATIC,):
         # resident: (3 + 5 enabled chains) x 2 launches; push: (2 + 3 enabled chains) x 4 frames
-        assert out.stdout.strip().splitlines()[-1] == "rails ok 16 20", (env, out.stdout[-500:])
+        assert _rails3_run(nv, cases, forms) == (16, 20), forms
