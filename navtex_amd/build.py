@@ -1,7 +1,7 @@
 """Build helper: compiles libnavtex_amd.so (HIP kernels for gfx950 + host C/C++) and its
-companions libnavtex_amd_scan.so (the band scan, navtex_amd/scan/) and libnavtex_amd_resample.so (the resampler,
-navtex_amd/resample/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled reference seams via
-oracle/Makefile.
+companions libnavtex_amd_scan.so (the band scan, navtex_amd/scan/), libnavtex_amd_resample.so (the resampler,
+navtex_amd/resample/) and libnavtex_amd_ddc.so (the down-converter bank, navtex_amd/ddc/) in-tree with hipcc, and -- for
+tests only -- the oracle library and the compiled reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
     python navtex_amd/build.py --oracle   # + oracle (and reference seams when /root/reference exists)
@@ -38,6 +38,13 @@ RESAMPLE_LIB = PKG / "libnavtex_amd_resample.so"
 RESAMPLE_C_SOURCES = ["nvx_resample_design.c"]
 RESAMPLE_HIP_SOURCES = ["nvx_resample.hip"]
 RESAMPLE_CXX_SOURCES = ["nvx_resample_host.cpp"]
+# the third companion (include/navtex_amd_ddc.h): its own sources, plus the resampler's tap design compiled in (the object
+# the resampler links too: -fvisibility=hidden keeps its symbols out of both libraries' exports)
+DDC = PKG / "ddc"
+DDC_LIB = PKG / "libnavtex_amd_ddc.so"
+DDC_HIP_SOURCES = ["nvx_ddc.hip"]
+DDC_CXX_SOURCES = ["nvx_ddc_host.cpp"]
+DDC_SHARED_C_SOURCES = ["nvx_resample_design.c"]           # of RESAMPLE
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp"]
 
@@ -66,10 +73,14 @@ def _stale(out: Path, deps) -> bool:
     return any(Path(d).stat().st_mtime > t for d in deps)
 
 
-def _companion_jobs(hipcc: str, force: bool, src_dir: Path, c_sources, hip_sources, cxx_sources):
-    """(objects, compile jobs) of a companion library: csrc headers are on its include path (FIR1's taps)."""
+def _companion_jobs(hipcc: str, force: bool, src_dir: Path, c_sources, hip_sources, cxx_sources, also=()):
+    """(objects, compile jobs) of a companion library: csrc headers are on its include path (FIR1's taps), and the
+    directories in `also` (another companion's internal headers)."""
     headers = list(src_dir.glob("*.h")) + list(CSRC.glob("*.h")) + list((ROOT / "include").glob("*.h")) + [Path(__file__)]
     flags = [*COMMON, f"-I{src_dir}"]
+    for d in also:
+        headers += list(d.glob("*.h"))
+        flags.append(f"-I{d}")
     objs, jobs = [], []
     for srcs, cmd in ((c_sources, [hipcc, "-x", "c", "-std=gnu11", "-Wall", "-Wextra"]),
                       (hip_sources, [hipcc, f"--offload-arch={ARCH}", "-std=c++17"]),
@@ -90,6 +101,11 @@ def _resample_jobs(hipcc: str, force: bool):
     return _companion_jobs(hipcc, force, RESAMPLE, RESAMPLE_C_SOURCES, RESAMPLE_HIP_SOURCES, RESAMPLE_CXX_SOURCES)
 
 
+def _ddc_jobs(hipcc: str, force: bool):
+    objs, jobs = _companion_jobs(hipcc, force, DDC, [], DDC_HIP_SOURCES, DDC_CXX_SOURCES, also=(RESAMPLE,))
+    return objs + [OBJ / (src + ".o") for src in DDC_SHARED_C_SOURCES], jobs
+
+
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
     # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
     tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
@@ -107,6 +123,8 @@ def build_lib(force: bool = False) -> Path:
     jobs += scan_jobs
     resample_objs, resample_jobs = _resample_jobs(hipcc, force)
     jobs += resample_jobs
+    ddc_objs, ddc_jobs = _ddc_jobs(hipcc, force)
+    jobs += ddc_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -131,6 +149,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, SCAN_LIB, scan_objs, ["-lpthread", "-lm"])
     if force or _stale(RESAMPLE_LIB, resample_objs):
         _link(hipcc, RESAMPLE_LIB, resample_objs, ["-lpthread", "-lm"])
+    if force or _stale(DDC_LIB, ddc_objs):
+        _link(hipcc, DDC_LIB, ddc_objs, ["-lpthread", "-lm"])
     return LIB
 
 

@@ -5,9 +5,9 @@
 
 Compiles navtex_amd/csrc/nvx_cascade.hip of <git rev> and of the working tree for gfx950 (device only, -S) and compares
 the instruction streams of the kernels whose demangled names match in both (labels and comments removed).  With --all:
-every device translation unit of libnavtex_amd.so (navtex_amd/csrc/*.hip) and of the scan library (navtex_amd/scan/*.hip),
-which is how a feature that lives in a library of its own shows that it left those kernels alone
-(profiles/resample_isa_identical.txt).  Used in
+every device translation unit of libnavtex_amd.so (navtex_amd/csrc/*.hip), of the scan library (navtex_amd/scan/*.hip) and of
+the resampler (navtex_amd/resample/*.hip, where the revision has it), which is how a feature that lives in a library of its
+own shows that it left those kernels alone (profiles/resample_isa_identical.txt, profiles/ddc_isa_identical.txt).  Used in
 round 5 to show that pruning the A/B alternates out of the roofline kernel changed no instruction of the kernels that
 ship (profiles/r05/a0_prune_isa_identical.txt); hipcc cross-compiles, no GPU needed."""
 import re
@@ -23,7 +23,7 @@ def compile_tree(tree: Path, out: Path, everything: bool = False) -> dict:
     csrc = tree / "navtex_amd" / "csrc"
     sources = [csrc / "nvx_cascade.hip"]
     if everything:
-        sources = sorted(csrc.glob("*.hip")) + sorted((tree / "navtex_amd" / "scan").glob("*.hip"))
+        sources = sorted(csrc.glob("*.hip")) + sorted((tree / "navtex_amd" / "scan").glob("*.hip")) + sorted((tree / "navtex_amd" / "resample").glob("*.hip"))
     text = ""
     for src in sources:
         subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", f"-I{tree / 'include'}", f"-I{csrc}",
@@ -53,7 +53,9 @@ def main():
     with tempfile.TemporaryDirectory() as td:
         old = Path(td) / "old"
         old.mkdir()
-        tar = subprocess.run(["git", "-C", str(ROOT), "archive", rev, "navtex_amd/csrc", *(["navtex_amd/scan"] if everything else []), "include"], check=True, capture_output=True).stdout
+        extra = [d for d in ("navtex_amd/scan", "navtex_amd/resample") if everything and
+                 subprocess.run(["git", "-C", str(ROOT), "cat-file", "-e", f"{rev}:{d}"], capture_output=True).returncode == 0]
+        tar = subprocess.run(["git", "-C", str(ROOT), "archive", rev, "navtex_amd/csrc", *extra, "include"], check=True, capture_output=True).stdout
         subprocess.run(["tar", "x", "-C", str(old)], input=tar, check=True)
         a = {canonical(k): v for k, v in compile_tree(old, Path(td) / "a.s", everything).items()}
         b = compile_tree(ROOT, Path(td) / "b.s", everything)
