@@ -9,7 +9,7 @@ from fractions import Fraction
 
 import numpy as np
 
-from resample_ref import convert, resample
+from resample_ref import convert, resample, resample_streams
 
 N, SCALE, GUARD_HZ = 4096, 32767, 25000
 
@@ -62,9 +62,16 @@ def _table_tuple():
     return tuple(out)
 
 
+@functools.lru_cache(maxsize=None)
+def _table_array() -> np.ndarray:
+    w = np.array(_table_tuple(), dtype=np.int64)
+    w.setflags(write=False)
+    return w
+
+
 def table() -> np.ndarray:
     """W [N, 2] int64: (rint(32767 cos(2 pi j / N)), rint(32767 sin(2 pi j / N)))."""
-    return np.array(_table_tuple(), dtype=np.int64)
+    return _table_array().copy()
 
 
 def mix(x: np.ndarray, k: int, n_first: int) -> np.ndarray:
@@ -72,7 +79,7 @@ def mix(x: np.ndarray, k: int, n_first: int) -> np.ndarray:
     x = np.asarray(x, dtype=np.int64).reshape(-1, 2)
     if k == 0 or len(x) == 0:
         return x.copy()
-    w = table()
+    w = _table_array()
     assert 0 <= n_first < 1 << 50 and abs(k) <= N                            # k n stays inside int64
     j = (k * (n_first + np.arange(len(x), dtype=np.int64))) % N              # floor modulo: 0 .. N-1 for negative k too
     c, s = w[j, 0], w[j, 1]
@@ -97,6 +104,16 @@ def ddc(x: np.ndarray, taps: np.ndarray, L: int, M: int, k: int, consumed: int =
     hm[T - 1 - (consumed - first):] = mix(hist[T - 1 - (consumed - first):], k, first)
     out, _ = resample(mix(x, k, consumed), taps, L, M, consumed, hm)
     return out, np.concatenate([hist, x])[-(T - 1):]
+
+
+def ddc_slices(x: np.ndarray, taps: np.ndarray, L: int, M: int, ks, block: int = 256) -> np.ndarray:
+    """Every slice of one input from its reset, `block` slices at a time: the slices' mixed samples side by side through
+    resample_streams (one matrix product per 256 outputs, exact in float64).  x [n, 2] int64 (converted) -> int16
+    [len(ks), n_out, 2]; the words are ddc()'s (tests/test_ddc.py holds the two against each other)."""
+    x = np.asarray(x, dtype=np.int64).reshape(-1, 2)
+    ks = [int(k) for k in ks]
+    parts = [resample_streams(np.stack([mix(x, k, 0) for k in ks[b:b + block]]), taps, L, M, out_block=256) for b in range(0, len(ks), block)]
+    return np.concatenate(parts)
 
 
 def ddc_all(samples: np.ndarray, fmt: int, taps: np.ndarray, L: int, M: int, k: int, consumed: int = 0) -> np.ndarray:

@@ -213,6 +213,69 @@ def test_the_mixers_spurs_stay_below_the_front_ends_bar(k, amplitude):
     assert worst <= -76.0
 
 
+@pytest.mark.parametrize("k", [1, -1, 37, 512, -1365, dr.k_range(2400000)])
+def test_the_restated_mixer_against_a_plain_rotation_in_long_double(k):
+    """The restatement is exact integer arithmetic; this holds it against something that is not: (32767 / 32768) x
+    e^(-2 pi i j / N) in np.longdouble on 200 000 full-scale random samples from sample 12 345 on.  Where neither component
+    of the rotation comes within 68 of a rail (or beyond one), both components of dr.mix lie within 1.5 of it: 0.5 from the
+    rounding shift, plus (|I| + |Q|) 0.5 / 32768 <= 1.0 from the table's rounding (each of c and s is off by at most 0.5,
+    and |I|, |Q| <= 32768).  Measured: 1.282 at the worst of the six shifts (k = 2005); the bound asserted is the derived one."""
+    n, first = 200000, 12345
+    x = np.random.default_rng(5000 + k).integers(-32768, 32768, size=(n, 2))
+    j = (k * (first + np.arange(n, dtype=np.int64))) % dr.N                  # the index reduced exactly: the angle stays below one turn
+    ang = 2 * np.longdouble(np.pi) * j.astype(np.longdouble) / dr.N
+    assert np.finfo(np.longdouble).eps <= 2.0 ** -52
+    c, s = np.cos(ang), np.sin(ang)
+    xi, xq = x[:, 0].astype(np.longdouble), x[:, 1].astype(np.longdouble)
+    g = np.longdouble(32767) / np.longdouble(32768)
+    want = np.stack([g * (xi * c + xq * s), g * (xq * c - xi * s)], axis=1)
+    inside = np.all((want >= -32768 + 68) & (want <= 32767 - 68), axis=1)
+    assert inside.sum() > n // 4
+    got = dr.mix(x, k, first)
+    worst = float(np.abs(got[inside].astype(np.longdouble) - want[inside]).max())
+    print(f"k {k}: {int(inside.sum())} samples away from the rails, worst |mix - rotation| {worst:.3f}")
+    assert worst <= 1.5
+
+
+def test_every_table_index_at_the_rails_is_exact_in_32_bits():
+    """The header's "the sums are exact in 32 bits": for all 4096 j and the four rail pairs of (I, Q) both mixer sums with
+    their rounding constant stay below 2^31 in size, counted in Python integers from the decimal table; and the restated
+    mixer gives the clamp of that exact value."""
+    w = dr._table_tuple()
+    assert len(w) == dr.N
+    largest = 0
+    for i, q in ((32767, 32767), (-32768, -32768), (32767, -32768), (-32768, 32767)):
+        want = []
+        for c, s in w:
+            si, sq = i * c + q * s + (1 << 14), q * c - i * s + (1 << 14)
+            largest = max(largest, abs(si), abs(sq))
+            want.append((min(max(si >> 15, -32768), 32767), min(max(sq >> 15, -32768), 32767)))
+        got = dr.mix(np.full((dr.N, 2), (i, q), dtype=np.int64), 1, 0)       # k = 1 from sample 0: j = n
+        assert np.array_equal(got, np.array(want, dtype=np.int64)), (i, q)
+        assert got.max() == 32767 and got.min() == -32768                    # the clamp is reached on both sides
+    assert 2 ** 30 < largest < 2 ** 31, largest
+
+
+def test_the_block_route_for_many_slices_is_the_restatement_slice_by_slice():
+    """dr.ddc_slices, the reference of the GPU tests with thousands of slices, against dr.ddc: random taps of the 2.4 MS/s
+    shape, 2 inputs x 40 slices (k = 0 and both ends of the range among them), blocks of 256 and of 7 slices."""
+    fi = 2400000
+    L, M = rr.ratio(fi)
+    rng = np.random.default_rng(17)
+    taps = rng.integers(-400, 400, size=(L, 68)).astype(np.int16)
+    kmax = dr.k_range(fi)
+    ks = [0, 1, -1, kmax, -kmax, 1024, 2048 - 64] + [int(k) for k in rng.integers(-kmax, kmax + 1, size=33)]
+    assert len(ks) == 40
+    for seed in (1, 2):
+        x = np.random.default_rng(seed).integers(-32768, 32768, size=(3001, 2))
+        got = dr.ddc_slices(x, taps, L, M, ks)
+        assert got.dtype == np.int16 and got.shape == (40, rr.outputs_after(3001, L, M), 2)
+        for s, k in enumerate(ks):
+            assert np.array_equal(got[s], dr.ddc(x, taps, L, M, k)[0]), (seed, s, k)
+        assert np.array_equal(dr.ddc_slices(x, taps, L, M, ks, block=7), got)
+        assert len({got[s].tobytes() for s in range(40)}) == 40
+
+
 # ------------------------------------------------------------------------------------------------------------ end to end
 def test_one_wide_input_three_stations_end_to_end_on_the_cpu(nv, dd, oracle):
     """One 2.4 MS/s unsigned 8-bit input holds three stations with different texts (tests/ddc_cases.py); three slices
