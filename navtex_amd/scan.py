@@ -46,6 +46,7 @@ def _load() -> C.CDLL:
         "nvx_scan_last_error": (C.c_char_p, []),
         "nvx_scan_params_default": (None, [C.POINTER(Params)]),
         "nvx_scan_find": (i, [vp, C.POINTER(Params), C.POINTER(Hit), i]),
+        "nvx_scan_debug_last_launch": (C.c_int64, [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(sz)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -123,3 +124,10 @@ def time_stats(reset: bool = False) -> Tuple[float, int]:
     s, n = C.c_double(), C.c_uint64()
     _check(lib.nvx_scan_time_stats(C.byref(s), C.byref(n), int(reset)), "nvx_scan_time_stats")
     return s.value, n.value
+
+
+def debug_last_launch() -> dict:
+    """For tests (nvx_scan_debug_last_launch): the form, first grid and scratch of the last launch as the host handed it over."""
+    form, gx, gy, scratch = C.c_int(0), C.c_int(0), C.c_int(0), C.c_size_t(0)
+    n = lib.nvx_scan_debug_last_launch(C.byref(form), C.byref(gx), C.byref(gy), C.byref(scratch))
+    return dict(launches=n, form=form.value, grid=(gx.value, gy.value), scratch_bytes=scratch.value)

@@ -314,12 +314,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void nvx_scan_fold(nvx_scan_args a)
     a.power[(size_t)blockIdx.y * NVX_SCAN_FFT + b] = total;
 }
 
-hipError_t nvx_scan_launch(const nvx_scan_args *a, int form, hipStream_t s)
+hipError_t nvx_scan_launch(const nvx_scan_args *a, int form, hipStream_t s, dim3 *first_grid)
 {
+    const dim3 grid = form == 1 ? dim3(a->n_streams) : dim3(a->n_frames, a->n_streams);
+    *first_grid = grid;
     if (form == 1) {
-        hipLaunchKernelGGL(nvx_scan_stream, dim3(a->n_streams), dim3(SCAN_THREADS), 0, s, *a);
+        hipLaunchKernelGGL(nvx_scan_stream, grid, dim3(SCAN_THREADS), 0, s, *a);
     } else {
-        hipLaunchKernelGGL(nvx_scan_frame, dim3(a->n_frames, a->n_streams), dim3(SCAN_THREADS), 0, s, *a);
+        hipLaunchKernelGGL(nvx_scan_frame, grid, dim3(SCAN_THREADS), 0, s, *a);
         hipLaunchKernelGGL(nvx_scan_fold, dim3(NVX_SCAN_FFT / SCAN_THREADS, a->n_streams), dim3(SCAN_THREADS), 0, s, *a);
     }
     return hipGetLastError();

@@ -71,6 +71,8 @@ static struct ScanState {
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pool, pending;
     double sum_ms = 0.0; uint64_t n = 0;
+    struct { int form; dim3 grid; size_t scratch_bytes; } last = {};        // nvx_scan_debug_last_launch
+    int64_t launches = 0;
 } g_st;
 
 static const size_t SCRATCH_ROWS_MAX = 16384;       // form 2's frame rows: 256 MB
@@ -100,6 +102,18 @@ extern "C" int nvx_scan_time_stats(double *sum_ms, uint64_t *launches, int reset
     if (launches) *launches = g_st.n;
     if (reset) { g_st.sum_ms = 0.0; g_st.n = 0; }
     return NVX_OK;
+}
+
+extern "C" int64_t nvx_scan_debug_last_launch(int *form, int *grid_x, int *grid_y, size_t *scratch_bytes)
+{
+    std::lock_guard<std::mutex> lk(g_st.mu);
+    if (g_st.launches) {
+        if (form) *form = g_st.last.form;
+        if (grid_x) *grid_x = (int)g_st.last.grid.x;
+        if (grid_y) *grid_y = (int)g_st.last.grid.y;
+        if (scratch_bytes) *scratch_bytes = g_st.last.scratch_bytes;
+    }
+    return g_st.launches;
 }
 
 static int scan_mode(int raw_rate, int stage0_order, const char *what, int *mode)
@@ -160,9 +174,16 @@ extern "C" int nvx_scan_resident(int device, const void *d_iq, size_t pitch_samp
     if (form == 2 && !rows_fit) form = 1;
 
     hipStream_t s = (hipStream_t)hip_stream;
-    if (form == 2) HIP_TRY(hipMallocAsync((void **)&a.rows, (size_t)n_streams * n_frames * NVX_SCAN_FFT * sizeof(double), s));
+    const size_t scratch_bytes = form == 2 ? (size_t)n_streams * n_frames * NVX_SCAN_FFT * sizeof(double) : 0;
+    if (form == 2) HIP_TRY(hipMallocAsync((void **)&a.rows, scratch_bytes, s));
     if (timed) HIP_TRY(hipEventRecord(ev.first, s));
-    HIP_TRY(nvx_scan_launch(&a, form, s));
+    {
+        std::lock_guard<std::mutex> lk(g_st.mu);
+        dim3 grid;
+        HIP_TRY(nvx_scan_launch(&a, form, s, &grid));
+        g_st.last = { form, grid, scratch_bytes };
+        g_st.launches++;
+    }
     if (timed) {
         HIP_TRY(hipEventRecord(ev.second, s));
         std::lock_guard<std::mutex> lk(g_st.mu);

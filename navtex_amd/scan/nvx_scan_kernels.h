@@ -27,7 +27,13 @@ struct nvx_scan_args {
     double *rows;             // form 2: [n_streams][n_frames][2048] frame rows
 };
 
-// form 1: nvx_scan_stream; form 2: nvx_scan_frame + nvx_scan_fold (a->rows must be set)
-hipError_t nvx_scan_launch(const nvx_scan_args *a, int form, hipStream_t s);
+// form 1: nvx_scan_stream; form 2: nvx_scan_frame + nvx_scan_fold (a->rows must be set).  *first_grid: the grid of the
+// first kernel as it was launched
+hipError_t nvx_scan_launch(const nvx_scan_args *a, int form, hipStream_t s, dim3 *first_grid);
+
+// For tests: what the last nvx_scan_resident handed nvx_scan_launch -- the form taken (1 or 2), the grid of the first
+// kernel, and the bytes of form 2's scratch (0 in form 1).  Returns the launches made by this process so far (0: nothing
+// was written); any pointer may be NULL.
+extern "C" NVX_API int64_t nvx_scan_debug_last_launch(int *form, int *grid_x, int *grid_y, size_t *scratch_bytes);
 
 #endif

@@ -5,12 +5,15 @@
 #include <stdio.h>
 #include <stdint.h>
 #include "navtex_amd_scan.h"
+/* the tests' hook, declared in navtex_amd/scan/nvx_scan_kernels.h (a HIP header) and not in the public one */
+int64_t nvx_scan_debug_last_launch(int *form, int *grid_x, int *grid_y, size_t *scratch_bytes);
 #define EXPECT(expr, want) do { int r_ = (expr); printf("%-96s -> %d\n", #expr, r_); if (r_ != (want)) bad++; } while (0)
 static double row[NVX_SCAN_FFT];
 static int16_t few[2 * 1024];
 int main(void)
 {
-    int bad = 0, used = -1;
+    int bad = 0, used = -1, form = -7, gx = -7, gy = -7;
+    size_t scratch = 77;
     uint64_t n = 7;
     double ms = -1.0;
     void *in = (void *)(uintptr_t)0x100000, *out = (void *)(uintptr_t)0x200000;      /* never dereferenced: refused first */
@@ -45,6 +48,10 @@ int main(void)
     EXPECT(nvx_scan_time_stats(&ms, &n, 1), NVX_OK);
     EXPECT(ms == 0.0 && n == 0, 1);
     EXPECT(nvx_scan_last_error() != NULL && nvx_scan_last_error()[0] != 0, 1);
+    EXPECT((int)nvx_scan_debug_last_launch(NULL, NULL, NULL, NULL), 0);                       /* nothing was launched above */
+    EXPECT((int)nvx_scan_debug_last_launch(&form, NULL, &gy, NULL), 0);
+    EXPECT((int)nvx_scan_debug_last_launch(&form, &gx, &gy, &scratch), 0);
+    EXPECT(form == -7 && gx == -7 && gy == -7 && scratch == 77, 1);                           /* and nothing written */
 
     nvx_scan_params_default(NULL);
     nvx_scan_params_default(&p);

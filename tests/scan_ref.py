@@ -99,10 +99,15 @@ def fft(xr: np.ndarray, xi: np.ndarray):
     return xr, xi
 
 
+def slot_powers(y1: np.ndarray, first_frame: int, n_frames: int) -> np.ndarray:
+    """[n_frames, 9, 2048]: every slot's powers by bin, before any sum."""
+    xr, xi = fft(*window(segments(y1, first_frame, n_frames)))
+    return xr * xr + xi * xi
+
+
 def power_row(y1: np.ndarray, first_frame: int, n_frames: int) -> np.ndarray:
     """The scan's row [2048] of frames [first_frame, first_frame + n_frames) of the stream whose FIR1 output is y1."""
-    xr, xi = fft(*window(segments(y1, first_frame, n_frames)))
-    p = xr * xr + xi * xi                                          # [n_frames, 9, 2048]
+    p = slot_powers(y1, first_frame, n_frames)
     total = np.zeros(N)
     for f in range(n_frames):
         row = np.zeros(N)
@@ -117,6 +122,19 @@ def scan(iq: np.ndarray, raw: bool, stage0_order: int = 1, first_frame: int = 0,
     if n_frames is None:
         n_frames = y1.shape[0] // FRAME_Y1 - first_frame
     return power_row(y1, first_frame, n_frames)
+
+
+FRAME_IN, FRAME_RAW = 4 * FRAME_Y1, 32 * FRAME_Y1
+
+
+def power_row_of_cut(cut: np.ndarray, raw: bool, stage0_order: int, n_frames: int) -> np.ndarray:
+    """The scan's row of frames [f0, f0 + n_frames) of a stream from `cut`, its samples from frame f0 on: the header's
+    lead-in claim restated -- the 16 outputs in front of a slot's segment take up everything the filters remember, so
+    the filters may as well start from their reset at the frame's first sample, and nothing behind the frames is read.
+    tests/test_scan.py holds this against power_row over the whole stream."""
+    n = n_frames * (FRAME_RAW if raw else FRAME_IN)
+    assert len(cut) >= n
+    return power_row(front(cut[:n], raw, stage0_order), 0, n_frames)
 
 
 # ------------------------------------------------------------------------------------------------------------ detector

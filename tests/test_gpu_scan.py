@@ -100,8 +100,13 @@ def test_the_default_form_follows_the_shape_and_both_are_launched(nv, sc):
     buf = _upload(nv, [iq] * n, pitch)
     want = sr.power_row(sr.front(iq, raw), 0, frames)
     sc.set_form(0)
+    launches = sc.debug_last_launch()["launches"]
     big = sc.scan_resident(buf, pitch, 0, frames, n, raw)
+    last = sc.debug_last_launch()
+    assert last["form"] == 1 and last["grid"] == (n, 1) and last["scratch_bytes"] == 0 and last["launches"] == launches + 1, last
     small = sc.scan_resident(buf, pitch, 0, frames, 7, raw)
+    last = sc.debug_last_launch()
+    assert last["form"] == 2 and last["grid"] == (frames, 7) and last["scratch_bytes"] == 7 * frames * sc.FFT * 8 and last["launches"] == launches + 2, last
     assert all(np.array_equal(_u64(big[s]), _u64(want)) for s in range(n))
     assert all(np.array_equal(_u64(small[s]), _u64(want)) for s in range(7))
     buf.free()

@@ -21,6 +21,7 @@ ROOT = Path(__file__).resolve().parent.parent
 HEADER = ROOT / "include" / "navtex_amd_scan.h"
 SYMBOLS = ["nvx_scan_find", "nvx_scan_iq", "nvx_scan_last_error", "nvx_scan_params_default", "nvx_scan_resident",
            "nvx_scan_set_form", "nvx_scan_time_stats", "nvx_scan_timing"]
+HOOK = "nvx_scan_debug_last_launch"        # the tests' one hook: declared in nvx_scan_kernels.h, not in the public header
 
 
 @pytest.fixture(scope="module")
@@ -49,7 +50,7 @@ def test_header_compiles_as_plain_c_and_declares_the_entry_points(tmp_path):
     assert subprocess.run([str(tmp_path / "t")]).returncode == 0
 
 
-@pytest.mark.parametrize("sym", SYMBOLS)
+@pytest.mark.parametrize("sym", SYMBOLS + [HOOK])
 def test_symbol_is_exported(sc, sym):
     assert hasattr(sc.lib, sym), f"{sym} is declared in navtex_amd_scan.h but not exported"
 
@@ -57,6 +58,14 @@ def test_symbol_is_exported(sc, sym):
 def test_the_companion_links_neither_the_product_library_nor_test_infrastructure(sc):
     out = subprocess.run(["ldd", str(ROOT / "navtex_amd" / "libnavtex_amd_scan.so")], capture_output=True, text=True).stdout
     assert "libnavtex_amd.so" not in out and "oracle" not in out and "libamdhip64" in out
+
+
+def test_the_hook_is_internal_and_the_library_defines_nothing_else(sc):
+    nm = subprocess.run(["nm", "-D", str(ROOT / "navtex_amd" / "libnavtex_amd_scan.so")], capture_output=True, text=True, check=True).stdout
+    defined = sorted(l.split()[-1] for l in nm.splitlines() if " T " in l and "nvx_" in l)
+    assert defined == sorted(SYMBOLS + [HOOK]) and HOOK not in HEADER.read_text()
+    assert HOOK in (ROOT / "navtex_amd" / "scan" / "nvx_scan_kernels.h").read_text()
+    assert sc.lib.nvx_scan_debug_last_launch(None, None, None, None) >= 0 and set(sc.debug_last_launch()) == {"launches", "form", "grid", "scratch_bytes"}
 
 
 def test_null_and_nonsense_arguments_are_errors_never_crashes(sc, tmp_path):
@@ -67,7 +76,7 @@ def test_null_and_nonsense_arguments_are_errors_never_crashes(sc, tmp_path):
                     f"-Wl,-rpath,{lib}", "-Wl,-rpath,/opt/rocm/lib", "-lm"], check=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0 and "scan null-safety ok" in out.stdout, (out.stdout[-2500:], out.stderr[-500:])
-    assert all(re.search(rf"\b{s}\(", src.read_text()) for s in SYMBOLS)
+    assert all(re.search(rf"\b{s}\(", src.read_text()) for s in SYMBOLS + [HOOK])
 
 
 def test_device_entry_points_return_nodev_without_a_gpu(nv, sc):
@@ -158,6 +167,26 @@ def test_the_restated_transform_is_numpys_fft(nv):
         dev = np.max(np.abs((fr + 1j * fi) - ref)) / np.max(np.abs(ref))
         print(name, "worst relative deviation", dev)
         assert dev <= 4 * FFT_MEASURED, (name, dev)
+
+
+@pytest.mark.parametrize("f0", [1, 2])
+@pytest.mark.parametrize("raw,s0", [(True, 1), (True, 3), (False, 1)], ids=["raw", "raw-cic3", "252k"])
+def test_the_restatement_on_a_cut_is_the_restatement_on_the_whole_stream(nv, raw, s0, f0):
+    """The header's lead-in claim, which the GPU tests of long rows lean on: frames [f0, f0 + 2) restated from the samples
+    of those frames alone equal, word for word, the same frames restated from the stream's reset -- with full-scale noise
+    in front of the cut and behind it, so that anything the filters carried across a frame's first sample would show."""
+    frame = nv.FRAME_RAW if raw else nv.FRAME_IN
+    rate = nv.RATE_RAW if raw else nv.RATE_IN
+    rng = np.random.default_rng(100 * f0 + s0 + raw)
+    st, _ = signals.stream_params(nv, 31 + f0, rate, freq_hz=-7001)
+    iq = rng.integers(-32768, 32768, size=((f0 + 3) * frame, 2)).astype(np.int16)
+    iq[f0 * frame:(f0 + 2) * frame] = nv.synth_host(st, rate, 2 * frame, f0 * frame)
+    whole = sr.power_row(sr.front(iq, raw, s0), f0, 2)
+    cut = sr.power_row_of_cut(iq[f0 * frame:], raw, s0, 2)
+    assert whole.any() and np.array_equal(whole.view(np.uint64), cut.view(np.uint64))
+    for k in (0, 1):                                                 # and frame by frame
+        one = sr.power_row_of_cut(iq[(f0 + k) * frame:], raw, s0, 1)
+        assert np.array_equal(one.view(np.uint64), sr.power_row(sr.front(iq, raw, s0), f0 + k, 1).view(np.uint64))
 
 
 def test_a_synthetic_carrier_at_plus_14000_lands_at_plus_14000(nv):
