@@ -74,8 +74,9 @@ def _stale(out: Path, deps) -> bool:
 
 
 def _companion_jobs(hipcc: str, force: bool, src_dir: Path, c_sources, hip_sources, cxx_sources, also=()):
-    """(objects, compile jobs) of a companion library: csrc headers are on its include path (FIR1's taps), and the
-    directories in `also` (another companion's internal headers)."""
+    """(objects, compile jobs) of a companion library: csrc headers are on its include path (FIR1's taps, and
+    nvx_companion.h: what the companions' host sides share), and the directories in `also` (another companion's internal
+    headers: the bank compiles the resampler's nvx_rs_host.h and nvx_rs_device.h)."""
     headers = list(src_dir.glob("*.h")) + list(CSRC.glob("*.h")) + list((ROOT / "include").glob("*.h")) + [Path(__file__)]
     flags = [*COMMON, f"-I{src_dir}"]
     for d in also:

@@ -5,15 +5,12 @@ import fails.  Device memory comes from the package's DeviceBuffer."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
 from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _native as N
+from . import _companion, _native as N
 
-_LIB_PATH = Path(os.environ.get("NAVTEX_AMD_DDC_LIB") or (Path(__file__).resolve().parent / "libnavtex_amd_ddc.so"))
 
 OUTPUT_RATE, GRID, SCALE, GUARD_HZ = 252000, 4096, 32767, 25000
 CS16, CU8, CS8, CF32 = 0, 1, 2, 3
@@ -27,13 +24,10 @@ class Config(C.Structure):
                 ("input_rate_hz", C.c_uint32), ("format", C.c_int)]
 
 
-def _load() -> C.CDLL:
-    if not _LIB_PATH.exists():
-        raise ImportError(f"{_LIB_PATH} is missing: build it with `python navtex_amd/build.py` (hipcc, gfx950)")
-    lib = C.CDLL(str(_LIB_PATH))
+def _signatures() -> dict:
     vp, sz, i, u32, u64, dbl = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint64, C.c_double
     ip, dp = C.POINTER(i), C.POINTER(dbl)
-    sig = {
+    return {
         "nvx_ddc_config_default": (None, [C.POINTER(Config)]),
         "nvx_ddc_create": (i, [C.POINTER(Config), C.POINTER(vp)]),
         "nvx_ddc_destroy": (None, [vp]),
@@ -52,25 +46,12 @@ def _load() -> C.CDLL:
         "nvx_ddc_debug_last_launch": (C.c_int64, [vp, ip, ip, ip, ip, ip, ip, ip, C.POINTER(sz)]),
         "nvx_ddc_debug_set_position": (i, [vp, i, u64]),
     }
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    return lib
 
 
-lib = _load()
+lib = _companion.load("NAVTEX_AMD_DDC_LIB", "libnavtex_amd_ddc.so", _signatures())
 
 
-class DdcError(N.NvxError):
-    def __init__(self, code: int, where: str):
-        self.code = code
-        RuntimeError.__init__(self, f"{where}: error {code}: {lib.nvx_ddc_last_error().decode(errors='replace')}")
-
-
-def _check(rc: int, where: str) -> int:
-    if rc < 0:
-        raise DdcError(rc, where)
-    return rc
+DdcError, _check = _companion.errors("DdcError", __name__, lib.nvx_ddc_last_error)
 
 
 def grid(input_rate_hz: int, hz: float) -> Tuple[int, float]:
@@ -87,8 +68,9 @@ def table() -> np.ndarray:
     return w
 
 
-class Ddc:
+class Ddc(_companion.Handle):
     """nvx_ddc wrapper: n_inputs inputs at input_rate_hz in `format` -> n_slices packed int16 IQ rows at 252 kS/s each."""
+    _destroy = lib.nvx_ddc_destroy
 
     def __init__(self, input_rate_hz: int, format: int = CU8, n_inputs: int = 1, n_slices: int = 1, device: int = 0):
         cfg = Config()
@@ -160,17 +142,3 @@ class Ddc:
     def debug_set_position(self, consumed: int, input: int = -1) -> None:
         """For tests (nvx_ddc_debug_set_position): the input stands at `consumed` with silence in front."""
         _check(lib.nvx_ddc_debug_set_position(self._h, input, consumed), "nvx_ddc_debug_set_position")
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            lib.nvx_ddc_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        self.close()

@@ -1,6 +1,7 @@
 /* nvx_ddc_plan.h -- what the down-converter bank's host side (nvx_ddc_host.cpp) and its kernels (nvx_ddc.hip) share, and
  * the tests' two hooks.  Internal.  The tile geometry, the tap table's layout and the design (L, M, T, taps) are the
- * resampler's: navtex_amd/resample/nvx_resample_plan.h and nvx_resample_design.c, compiled into this library. */
+ * resampler's, and so are the plan's host code and the kernels' common device code: navtex_amd/resample/nvx_resample_plan.h,
+ * nvx_rs_host.h, nvx_rs_device.h and nvx_resample_design.c, compiled into this library. */
 #ifndef NVX_DDC_PLAN_H
 #define NVX_DDC_PLAN_H
 
@@ -46,7 +47,7 @@ struct nvx_ddc_args {
 /* grid (chunks, n_slices, n_inputs) */
 hipError_t nvx_ddc_launch(const nvx_ddc_args *a, int format, int n_inputs, int chunks, bool taps_in_lds, hipStream_t s);
 size_t nvx_ddc_lds_bytes(const nvx_ddc_args *a, bool taps_in_lds);
-hipError_t nvx_ddc_prepare(void);
+void nvx_ddc_prepare(void);
 #endif
 
 #endif

@@ -5,15 +5,12 @@ import fails.  Device memory comes from the package's DeviceBuffer."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
 from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _native as N
+from . import _companion, _native as N
 
-_LIB_PATH = Path(os.environ.get("NAVTEX_AMD_RESAMPLE_LIB") or (Path(__file__).resolve().parent / "libnavtex_amd_resample.so"))
 
 OUTPUT_RATE, SHIFT = 252000, 15
 CS16, CU8, CS8, CF32 = 0, 1, 2, 3
@@ -27,13 +24,10 @@ class Config(C.Structure):
                 ("format", C.c_int)]
 
 
-def _load() -> C.CDLL:
-    if not _LIB_PATH.exists():
-        raise ImportError(f"{_LIB_PATH} is missing: build it with `python navtex_amd/build.py` (hipcc, gfx950)")
-    lib = C.CDLL(str(_LIB_PATH))
+def _signatures() -> dict:
     vp, sz, i, u32, u64 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32, C.c_uint64
     ip = C.POINTER(i)
-    sig = {
+    return {
         "nvx_resample_config_default": (None, [C.POINTER(Config)]),
         "nvx_resample_create": (i, [C.POINTER(Config), C.POINTER(vp)]),
         "nvx_resample_destroy": (None, [vp]),
@@ -50,25 +44,12 @@ def _load() -> C.CDLL:
         "nvx_resample_last_error": (C.c_char_p, []),
         "nvx_resample_debug_last_launch": (C.c_int64, [vp, ip, ip, ip, ip, ip, C.POINTER(sz)]),
     }
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    return lib
 
 
-lib = _load()
+lib = _companion.load("NAVTEX_AMD_RESAMPLE_LIB", "libnavtex_amd_resample.so", _signatures())
 
 
-class ResampleError(N.NvxError):
-    def __init__(self, code: int, where: str):
-        self.code = code
-        RuntimeError.__init__(self, f"{where}: error {code}: {lib.nvx_resample_last_error().decode(errors='replace')}")
-
-
-def _check(rc: int, where: str) -> int:
-    if rc < 0:
-        raise ResampleError(rc, where)
-    return rc
+ResampleError, _check = _companion.errors("ResampleError", __name__, lib.nvx_resample_last_error)
 
 
 def design(input_rate_hz: int) -> Tuple[int, int, int, int, np.ndarray]:
@@ -88,8 +69,9 @@ def out_count(input_rate_hz: int, consumed_before: int, n_in: int) -> int:
     return n
 
 
-class Resampler:
+class Resampler(_companion.Handle):
     """nvx_resampler wrapper: n_streams streams at input_rate_hz in `format` -> packed int16 IQ at 252 kS/s."""
+    _destroy = lib.nvx_resample_destroy
 
     def __init__(self, input_rate_hz: int, format: int = CS16, n_streams: int = 1, device: int = 0):
         cfg = Config()
@@ -149,17 +131,3 @@ class Resampler:
                                                       C.byref(lds)), "nvx_resample_debug_last_launch")
         return {"launches": n, "K": K.value, "tiles": tiles.value, "tiles_per_chunk": tpc.value, "chunks": chunks.value,
                 "taps_in_lds": bool(in_lds.value), "lds_bytes": lds.value}
-
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            lib.nvx_resample_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        self.close()

@@ -17,107 +17,9 @@
 //   come from the host, and the prologue's two small quotients from shifts and subtractions: the kernel divides nowhere.
 // The tap table (up to 60 KB) sits in the LDS behind the planes; a larger one (L large) is read from global memory
 // (TAPS_LDS = false), the same words at the same indices.  No fp64, float32 only in CF32's conversion, no atomics.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "nvx_resample_plan.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef short rs_short2 __attribute__((ext_vector_type(2)));
-// volatile: every access stays one ds_read_b64 (paired into ds_read2_b64 the LDS serves them at half the rate)
-typedef __attribute__((address_space(3))) volatile u32x2 lds_vu2;
-
-__device__ __forceinline__ int dot2(uint32_t x, uint32_t h, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(rs_short2, x), __builtin_bit_cast(rs_short2, h), acc, false);
-}
-// (a & 0xffff) | (b << 16) and (a >> 16) | (b & 0xffff0000) as one v_perm_b32 each: selector bytes 0-3 name a's bytes, 4-7 b's
-__device__ __forceinline__ uint32_t lo_pair(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); }
-__device__ __forceinline__ uint32_t hi_pair(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }
-// n = quot * d + rem for n < d << BITS, by shifts and subtractions
-template <int BITS>
-__device__ __forceinline__ void divmod(uint32_t n, uint32_t d, uint32_t &quot, uint32_t &rem)
-{
-    quot = 0;
-#pragma unroll
-    for (int b = BITS - 1; b >= 0; b--)
-        if (n >= (d << b)) { n -= d << b; quot |= 1u << b; }
-    rem = n;
-}
-__device__ __forceinline__ int clamp16(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
-
-// CF32: times 32768 in float32, to the nearest integer with ties to even, clamped; NaN -> 0
-__device__ __forceinline__ uint32_t cf32_to_i16(uint32_t bits)
-{
-    const float f = __builtin_bit_cast(float, bits);
-    const float y = __builtin_amdgcn_fmed3f(__builtin_rintf(f * 32768.0f), -32768.0f, 32767.0f);     // the clamp: one v_med3_f32
-    const int v = f != f ? 0 : (int)y;
-    return (uint32_t)v & 0xffffu;
-}
-
-template <int FMT> struct Fmt;
-template <> struct Fmt<NVX_RS_CS16> { static constexpr int BPS = 4, NV = 2, UNROLL = 4; };
-template <> struct Fmt<NVX_RS_CU8>  { static constexpr int BPS = 2, NV = 1, UNROLL = 4; };
-template <> struct Fmt<NVX_RS_CS8>  { static constexpr int BPS = 2, NV = 1, UNROLL = 4; };
-template <> struct Fmt<NVX_RS_CF32> { static constexpr int BPS = 8, NV = 4, UNROLL = 2; };
-
-// one sample of the row as a packed word (I low, Q high)
-template <int FMT>
-__device__ __forceinline__ uint32_t load_sample(const char *row, int idx)
-{
-    if constexpr (FMT == NVX_RS_CS16) {
-        return ((const uint32_t *)row)[idx];
-    } else if constexpr (FMT == NVX_RS_CU8) {
-        const uint32_t w = ((const uint16_t *)row)[idx];
-        return ((((w & 0xffu) << 8) | ((w & 0xff00u) << 16)) ^ 0x80808080u);
-    } else if constexpr (FMT == NVX_RS_CS8) {
-        const uint32_t w = ((const uint16_t *)row)[idx];
-        return ((w & 0xffu) << 8) | ((w & 0xff00u) << 16);
-    } else {
-        const uint2 w = ((const uint2 *)row)[idx];
-        return cf32_to_i16(w.x) | (cf32_to_i16(w.y) << 16);
-    }
-}
-
-// the 8 samples from sample s (a multiple of 8) of the row: NV 16-byte words, read once
-template <int FMT>
-__device__ __forceinline__ void load_group(const char *row, int s, u32x4 (&v)[Fmt<FMT>::NV])
-{
-    const u32x4 *p = (const u32x4 *)(row + (size_t)s * Fmt<FMT>::BPS);
-#pragma unroll
-    for (int i = 0; i < Fmt<FMT>::NV; i++) v[i] = __builtin_nontemporal_load(p + i);
-}
-
-// ... converted: 8 int16 of I and 8 of Q
-template <int FMT>
-__device__ __forceinline__ void convert_group(const u32x4 (&v)[Fmt<FMT>::NV], u32x4 &I, u32x4 &Q)
-{
-    if constexpr (FMT == NVX_RS_CS16) {
-        const uint32_t a0 = v[0].x, a1 = v[0].y, a2 = v[0].z, a3 = v[0].w, b0 = v[1].x, b1 = v[1].y, b2 = v[1].z, b3 = v[1].w;
-        I.x = lo_pair(a0, a1); I.y = lo_pair(a2, a3); I.z = lo_pair(b0, b1); I.w = lo_pair(b2, b3);
-        Q.x = hi_pair(a0, a1); Q.y = hi_pair(a2, a3); Q.z = hi_pair(b0, b1); Q.w = hi_pair(b2, b3);
-    } else if constexpr (FMT == NVX_RS_CU8 || FMT == NVX_RS_CS8) {
-        // a word holds I0 Q0 I1 Q1 as bytes: each becomes the high byte of its int16, and (2u - 255) * 128 = (u << 8) - 0x7f80
-        // is (u << 8) ^ 0x8080 in 16 bits
-        const uint32_t flip = FMT == NVX_RS_CU8 ? 0x80808080u : 0u;
-        const uint32_t w0 = v[0].x, w1 = v[0].y, w2 = v[0].z, w3 = v[0].w;
-        I.x = ((w0 << 8) & 0xff00ff00u) ^ flip; I.y = ((w1 << 8) & 0xff00ff00u) ^ flip;
-        I.z = ((w2 << 8) & 0xff00ff00u) ^ flip; I.w = ((w3 << 8) & 0xff00ff00u) ^ flip;
-        Q.x = (w0 & 0xff00ff00u) ^ flip; Q.y = (w1 & 0xff00ff00u) ^ flip;
-        Q.z = (w2 & 0xff00ff00u) ^ flip; Q.w = (w3 & 0xff00ff00u) ^ flip;
-    } else {
-        uint32_t i[4], q[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t f0 = v[k].x, f1 = v[k].y, f2 = v[k].z, f3 = v[k].w;
-            i[k] = cf32_to_i16(f0) | (cf32_to_i16(f2) << 16);
-            q[k] = cf32_to_i16(f1) | (cf32_to_i16(f3) << 16);
-        }
-        I.x = i[0]; I.y = i[1]; I.z = i[2]; I.w = i[3];
-        Q.x = q[0]; Q.y = q[1]; Q.z = q[2]; Q.w = q[3];
-    }
-}
+// The types, the small arithmetic, the formats' conversions and the launch of the eight instances live in
+// nvx_rs_device.h, which the down-converter bank's kernel file includes too.
+#include "nvx_rs_device.h"
 
 template <int FMT, bool TAPS_LDS>
 __global__ __launch_bounds__(NVX_RS_THREADS) void nvx_resample(const nvx_rs_args a)
@@ -165,7 +67,7 @@ __global__ __launch_bounds__(NVX_RS_THREADS) void nvx_resample(const nvx_rs_args
             u32x4 v[UNROLL][NV];
 #pragma unroll
             for (int u = 0; u < UNROLL; u++)
-                if (g + u * NVX_RS_THREADS < g1) load_group<FMT>(row, lo + (g + u * NVX_RS_THREADS) * NVX_RS_GROUP, v[u]);
+                if (g + u * NVX_RS_THREADS < g1) load_group<FMT, true>(row, lo + (g + u * NVX_RS_THREADS) * NVX_RS_GROUP, v[u]);
 #pragma unroll
             for (int u = 0; u < UNROLL; u++)
                 if (g + u * NVX_RS_THREADS < g1) {
@@ -228,24 +130,13 @@ __global__ __launch_bounds__(NVX_RS_THREADS) void nvx_resample(const nvx_rs_args
     }
 }
 
-template <int FMT, bool TAPS_LDS>
-static hipError_t launch(const nvx_rs_args *a, dim3 grid, size_t lds_bytes, hipStream_t s)
-{
-    hipLaunchKernelGGL((nvx_resample<FMT, TAPS_LDS>), grid, dim3(NVX_RS_THREADS), lds_bytes, s, *a);
-    return hipGetLastError();
-}
+struct resample_family {
+    template <int FMT, bool TAPS_LDS> static constexpr auto kernel = nvx_resample<FMT, TAPS_LDS>;
+};
 
 static const size_t LDS_MAX = NVX_RS_PLANE * 4 + NVX_RS_TAPS_LDS_MAX;
 
-hipError_t nvx_rs_prepare(void)
-{
-    const void *fns[] = { (const void *)nvx_resample<NVX_RS_CS16, true>, (const void *)nvx_resample<NVX_RS_CU8, true>,
-                          (const void *)nvx_resample<NVX_RS_CS8, true>, (const void *)nvx_resample<NVX_RS_CF32, true> };
-    // a runtime that does not know the attribute launches with whatever LDS the launch names; one that enforces it has it set
-    for (const void *f : fns)
-        if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS_MAX) != hipSuccess) (void)hipGetLastError();
-    return hipSuccess;
-}
+void nvx_rs_prepare(void) { nvx_rs_family_prepare<resample_family>(LDS_MAX); }
 
 size_t nvx_rs_lds_bytes(const nvx_rs_args *a, bool taps_in_lds)
 {
@@ -255,17 +146,5 @@ size_t nvx_rs_lds_bytes(const nvx_rs_args *a, bool taps_in_lds)
 hipError_t nvx_rs_launch(const nvx_rs_args *a, int format, int n_streams, int chunks, bool taps_in_lds, hipStream_t s)
 {
     const dim3 grid((unsigned)chunks, (unsigned)n_streams);
-    const size_t lds_bytes = nvx_rs_lds_bytes(a, taps_in_lds);
-    if (lds_bytes > LDS_MAX) return hipErrorInvalidValue;
-    switch (format * 2 + (taps_in_lds ? 1 : 0)) {
-    case NVX_RS_CS16 * 2 + 1: return launch<NVX_RS_CS16, true>(a, grid, lds_bytes, s);
-    case NVX_RS_CS16 * 2:     return launch<NVX_RS_CS16, false>(a, grid, lds_bytes, s);
-    case NVX_RS_CU8 * 2 + 1:  return launch<NVX_RS_CU8, true>(a, grid, lds_bytes, s);
-    case NVX_RS_CU8 * 2:      return launch<NVX_RS_CU8, false>(a, grid, lds_bytes, s);
-    case NVX_RS_CS8 * 2 + 1:  return launch<NVX_RS_CS8, true>(a, grid, lds_bytes, s);
-    case NVX_RS_CS8 * 2:      return launch<NVX_RS_CS8, false>(a, grid, lds_bytes, s);
-    case NVX_RS_CF32 * 2 + 1: return launch<NVX_RS_CF32, true>(a, grid, lds_bytes, s);
-    case NVX_RS_CF32 * 2:     return launch<NVX_RS_CF32, false>(a, grid, lds_bytes, s);
-    }
-    return hipErrorInvalidValue;
+    return nvx_rs_family_launch<resample_family>(a, format, taps_in_lds, grid, nvx_rs_lds_bytes(a, taps_in_lds), LDS_MAX, s);
 }

@@ -1,5 +1,6 @@
 /* nvx_resample_plan.h -- what the resampler's design (nvx_resample_design.c), its host side (nvx_resample_host.cpp) and
- * its kernels (nvx_resample.hip) share.  Internal. */
+ * its kernels (nvx_resample.hip) share.  Internal.  The plan's host code is nvx_rs_host.h, the kernels' common device code
+ * nvx_rs_device.h; the down-converter bank (navtex_amd/ddc/) compiles all three too. */
 #ifndef NVX_RESAMPLE_PLAN_H
 #define NVX_RESAMPLE_PLAN_H
 
@@ -66,7 +67,7 @@ struct nvx_rs_args {
 /* grid (chunks, n_streams); taps_in_lds: the table fits NVX_RS_TAPS_LDS_MAX */
 hipError_t nvx_rs_launch(const nvx_rs_args *a, int format, int n_streams, int chunks, bool taps_in_lds, hipStream_t s);
 size_t nvx_rs_lds_bytes(const nvx_rs_args *a, bool taps_in_lds);      /* the dynamic LDS of that launch */
-hipError_t nvx_rs_prepare(void);            /* once per process: the kernels' LDS limit */
+void nvx_rs_prepare(void);                  /* once per process: the kernels' LDS limit */
 #endif
 
 #endif

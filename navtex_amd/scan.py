@@ -5,15 +5,12 @@ import fails.  Device memory comes from the package's DeviceBuffer."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-from pathlib import Path
 from typing import List, Optional, Tuple
 
 import numpy as np
 
-from . import _native as N
+from . import _companion, _native as N
 
-_LIB_PATH = Path(os.environ.get("NAVTEX_AMD_SCAN_LIB") or (Path(__file__).resolve().parent / "libnavtex_amd_scan.so"))
 
 FFT, BIN_HZ, SLOTS_PER_FRAME = 2048, 30.76171875, 9
 
@@ -32,12 +29,9 @@ class Hit(C.Structure):
                 ("bin", C.c_int)]
 
 
-def _load() -> C.CDLL:
-    if not _LIB_PATH.exists():
-        raise ImportError(f"{_LIB_PATH} is missing: build it with `python navtex_amd/build.py` (hipcc, gfx950)")
-    lib = C.CDLL(str(_LIB_PATH))
+def _signatures() -> dict:
     vp, sz, i = C.c_void_p, C.c_size_t, C.c_int
-    sig = {
+    return {
         "nvx_scan_resident": (i, [i, vp, sz, sz, i, i, i, i, vp, vp]),
         "nvx_scan_iq": (i, [i, vp, sz, i, i, vp, C.POINTER(i)]),
         "nvx_scan_set_form": (i, [i]),
@@ -48,25 +42,12 @@ def _load() -> C.CDLL:
         "nvx_scan_find": (i, [vp, C.POINTER(Params), C.POINTER(Hit), i]),
         "nvx_scan_debug_last_launch": (C.c_int64, [C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(sz)]),
     }
-    for name, (res, args) in sig.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = res, args
-    return lib
 
 
-lib = _load()
+lib = _companion.load("NAVTEX_AMD_SCAN_LIB", "libnavtex_amd_scan.so", _signatures())
 
 
-class ScanError(N.NvxError):
-    def __init__(self, code: int, where: str):
-        self.code = code
-        RuntimeError.__init__(self, f"{where}: error {code}: {lib.nvx_scan_last_error().decode(errors='replace')}")
-
-
-def _check(rc: int, where: str) -> int:
-    if rc < 0:
-        raise ScanError(rc, where)
-    return rc
+ScanError, _check = _companion.errors("ScanError", __name__, lib.nvx_scan_last_error)
 
 
 def scan_resident_into(buf, pitch: int, first_frame: int, n_frames: int, n_streams: int, raw_rate: bool, stage0_order: int,

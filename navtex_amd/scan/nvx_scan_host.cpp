@@ -1,76 +1,18 @@
 // nvx_scan_host.cpp -- the band scan's device entry points (include/navtex_amd_scan.h): argument and span checks, the
 // choice of kernel form, HIP-event timing.  The library stands alone: it shares no state with libnavtex_amd.so.
-#include <hip/hip_runtime.h>
-
-#include <cstdarg>
-#include <cstdio>
 #include <mutex>
-#include <utility>
-#include <vector>
 
+#include "nvx_companion.h"
 #include "nvx_scan_kernels.h"
 
-static thread_local char g_err[512] = "";
+static const char NOUN[] = "the scan";
 
-static void set_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));
-static void set_error(const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof g_err, fmt, ap);
-    va_end(ap);
-}
-
-extern "C" const char *nvx_scan_last_error(void) { return g_err; }
-
-#define HIP_TRY(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-            return (e_ == hipErrorNoDevice || e_ == hipErrorInvalidDevice) ? NVX_ERR_NODEV : NVX_ERR_HIP; \
-        }                                                                                  \
-    } while (0)
-
-static int select_device(int device)
-{
-    int n = 0;
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n == 0) {
-        set_error("no HIP device available (%s); the scan has no CPU path", e == hipSuccess ? "device count 0" : hipGetErrorString(e));
-        return NVX_ERR_NODEV;
-    }
-    if (device < 0 || device >= n) { set_error("device %d out of range (0..%d)", device, n - 1); return NVX_ERR_ARG; }
-    HIP_TRY(hipSetDevice(device));
-    return NVX_OK;
-}
-
-// [p, p + bytes) against the allocation the runtime knows p to lie in; no verdict (NVX_OK) for a pointer it does not know
-static int check_device_span(const void *p, size_t bytes, const char *what)
-{
-    hipDeviceptr_t base = nullptr; size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return NVX_OK; }
-    const size_t off = (size_t)((const char *)p - (const char *)base);
-    if (off > size || bytes > size - off) {
-        set_error("%s: %zu bytes from %p leave the allocation they lie in (%zu bytes from %p): the launch would fault", what, bytes, p, size, (void *)base);
-        return NVX_ERR_ARG;
-    }
-    return NVX_OK;
-}
-
-// (a * b + c) * d without wrapping; false on overflow
-static bool span_bytes(size_t a, size_t b, size_t c, size_t d, size_t *out)
-{
-    size_t t;
-    return !__builtin_mul_overflow(a, b, &t) && !__builtin_add_overflow(t, c, &t) && !__builtin_mul_overflow(t, d, out);
-}
+extern "C" const char *nvx_scan_last_error(void) { return nvx_error_text(); }
 
 static struct ScanState {
     std::mutex mu;
     int form = 0;
-    bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool, pending;
-    double sum_ms = 0.0; uint64_t n = 0;
+    nvx_event_timer timer;
     struct { int form; dim3 grid; size_t scratch_bytes; } last = {};        // nvx_scan_debug_last_launch
     int64_t launches = 0;
 } g_st;
@@ -85,23 +27,12 @@ extern "C" int nvx_scan_set_form(int form)
     return NVX_OK;
 }
 
-extern "C" void nvx_scan_timing(int enable) { std::lock_guard<std::mutex> lk(g_st.mu); g_st.timing = enable != 0; }
+extern "C" void nvx_scan_timing(int enable) { std::lock_guard<std::mutex> lk(g_st.mu); g_st.timer.enabled = enable != 0; }
 
 extern "C" int nvx_scan_time_stats(double *sum_ms, uint64_t *launches, int reset)
 {
     std::lock_guard<std::mutex> lk(g_st.mu);
-    for (auto &p : g_st.pending) {
-        HIP_TRY(hipEventSynchronize(p.second));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, p.first, p.second));
-        g_st.sum_ms += ms; g_st.n++;
-        g_st.pool.push_back(p);
-    }
-    g_st.pending.clear();
-    if (sum_ms) *sum_ms = g_st.sum_ms;
-    if (launches) *launches = g_st.n;
-    if (reset) { g_st.sum_ms = 0.0; g_st.n = 0; }
-    return NVX_OK;
+    return g_st.timer.collect(sum_ms, launches, reset);
 }
 
 extern "C" int64_t nvx_scan_debug_last_launch(int *form, int *grid_x, int *grid_y, size_t *scratch_bytes)
@@ -149,24 +80,18 @@ extern "C" int nvx_scan_resident(int device, const void *d_iq, size_t pitch_samp
         set_error("%s: frames up to %zu need %zu samples per stream, the pitch is %zu", what, end_frame, row_end, pitch_samples);
         return NVX_ERR_ARG;
     }
-    if ((rc = select_device(device)) != NVX_OK) return rc;
-    if ((rc = check_device_span(d_iq, in_bytes, "nvx_scan_resident: input")) != NVX_OK) return rc;
-    if ((rc = check_device_span(d_power, out_bytes, "nvx_scan_resident: power rows")) != NVX_OK) return rc;
+    if ((rc = select_device(device, NOUN)) != NVX_OK) return rc;
+    if ((rc = check_device_span(d_iq, in_bytes, what, "input")) != NVX_OK) return rc;
+    if ((rc = check_device_span(d_power, out_bytes, what, "power rows")) != NVX_OK) return rc;
 
     nvx_scan_args a{};
     a.iq = (const uint32_t *)d_iq; a.pitch = pitch_samples; a.first_frame = first_frame;
     a.n_frames = n_frames; a.n_streams = n_streams; a.mode = mode; a.power = (double *)d_power;
 
-    int form; bool timed = false;
-    std::pair<hipEvent_t, hipEvent_t> ev{ nullptr, nullptr };
+    int form;
     {
         std::lock_guard<std::mutex> lk(g_st.mu);
         form = g_st.form;
-        if (g_st.timing) {
-            if (g_st.pool.empty()) { HIP_TRY(hipEventCreate(&ev.first)); HIP_TRY(hipEventCreate(&ev.second)); }
-            else { ev = g_st.pool.back(); g_st.pool.pop_back(); }
-            timed = true;
-        }
     }
     // a workgroup per stream fills the chip from about two workgroups per CU on; below that the frames are spread out too
     const bool rows_fit = (size_t)n_streams * (size_t)n_frames <= SCRATCH_ROWS_MAX && n_streams <= 65535;
@@ -176,18 +101,15 @@ extern "C" int nvx_scan_resident(int device, const void *d_iq, size_t pitch_samp
     hipStream_t s = (hipStream_t)hip_stream;
     const size_t scratch_bytes = form == 2 ? (size_t)n_streams * n_frames * NVX_SCAN_FFT * sizeof(double) : 0;
     if (form == 2) HIP_TRY(hipMallocAsync((void **)&a.rows, scratch_bytes, s));
-    if (timed) HIP_TRY(hipEventRecord(ev.first, s));
     {
         std::lock_guard<std::mutex> lk(g_st.mu);
+        nvx_event_timer::events ev;
         dim3 grid;
+        if ((rc = g_st.timer.begin(s, ev)) != NVX_OK) return rc;
         HIP_TRY(nvx_scan_launch(&a, form, s, &grid));
         g_st.last = { form, grid, scratch_bytes };
         g_st.launches++;
-    }
-    if (timed) {
-        HIP_TRY(hipEventRecord(ev.second, s));
-        std::lock_guard<std::mutex> lk(g_st.mu);
-        g_st.pending.push_back(ev);
+        if ((rc = g_st.timer.end(s, ev)) != NVX_OK) return rc;
     }
     if (form == 2) HIP_TRY(hipFreeAsync(a.rows, s));
     return NVX_OK;
@@ -204,7 +126,7 @@ extern "C" int nvx_scan_iq(int device, const int16_t *iq, size_t n, int raw_rate
         return NVX_ERR_ARG;
     }
     const int n_frames = (int)(n / frame_len);
-    if ((rc = select_device(device)) != NVX_OK) return rc;
+    if ((rc = select_device(device, NOUN)) != NVX_OK) return rc;
     const size_t bytes = (size_t)n_frames * frame_len * 4;
     void *d_iq = nullptr, *d_power = nullptr;
     hipError_t e = hipMalloc(&d_iq, bytes);

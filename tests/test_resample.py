@@ -1,7 +1,8 @@
 """The resampler (include/navtex_amd_resample.h) on the CPU: the header and the companion library's exports and argument
-safety, the rates and the count rule against exact rational arithmetic, the taps nvx_resample_design hands out (their
-properties and the prototype's response for the twelve rates of the header), the restatement (tests/resample_ref.py) on
-constants and at the rails, and resample -> decode end to end through the restatements."""
+safety, the plan's launch arithmetic against 128-bit integers (a stand-alone program under ASan + UBSan), the rates and the
+count rule against exact rational arithmetic, the taps nvx_resample_design hands out (their properties and the prototype's
+response for the twelve rates of the header), the restatement (tests/resample_ref.py) on constants and at the rails, and
+resample -> decode end to end through the restatements."""
 import ctypes as C
 import re
 import subprocess
@@ -97,6 +98,23 @@ def test_create_returns_nodev_without_a_gpu(nv, rs):
     with pytest.raises(nv.NvxError) as e:
         rs.Resampler(2400000, rs.CU8, n_streams=4)
     assert e.value.code == -2
+
+
+def test_the_launch_arithmetic_against_128_bit_integers_under_asan_ubsan(tmp_path):
+    """The plan's launch arithmetic (navtex_amd/resample/nvx_rs_host.h, which the down-converter bank compiles too) without
+    a device: for five plans, positions up to 2^62, output counts around a tile and every chunking, the kernels' walk
+    restated -- every output reached once, at its exact position and phase, inside the staged span, and the bounds the
+    kernels' two divisions rely on (tests/harness/rs_launch_args.cpp).  A stand-alone program under ASan + UBSan."""
+    exe = tmp_path / "rs_launch_args"
+    pkg = ROOT / "navtex_amd"
+    subprocess.run(["g++", "-g", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer",
+                    "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{ROOT / 'include'}", f"-I{pkg / 'csrc'}", f"-I{pkg / 'resample'}",
+                    str(ROOT / "tests" / "harness" / "rs_launch_args.cpp"), "-x", "c", str(pkg / "resample" / "nvx_resample_design.c"),
+                    "-o", str(exe), "-lm"], check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120, env={"ASAN_OPTIONS": "detect_leaks=1", "PATH": "/usr/bin:/bin"})
+    assert out.returncode == 0 and "rs launch args ok" in out.stdout, (out.stdout + out.stderr)[-3000:]
+    for rate in (2048000, 1000250, 252000, 96000, 100100):
+        assert f"{rate} S/s: " in out.stdout
 
 
 # ----------------------------------------------------------------------------------------------------- rates and counts

@@ -5,9 +5,11 @@
 
 Compiles navtex_amd/csrc/nvx_cascade.hip of <git rev> and of the working tree for gfx950 (device only, -S) and compares
 the instruction streams of the kernels whose demangled names match in both (labels and comments removed).  With --all:
-every device translation unit of libnavtex_amd.so (navtex_amd/csrc/*.hip), of the scan library (navtex_amd/scan/*.hip) and of
-the resampler (navtex_amd/resample/*.hip, where the revision has it), which is how a feature that lives in a library of its
-own shows that it left those kernels alone (profiles/resample_isa_identical.txt, profiles/ddc_isa_identical.txt).  Used in
+every device translation unit of libnavtex_amd.so (navtex_amd/csrc/*.hip), of the scan library (navtex_amd/scan/*.hip), of
+the resampler (navtex_amd/resample/*.hip) and of the down-converter bank (navtex_amd/ddc/*.hip, with the resampler's
+directory on its include path), each where the revision has it.  That is how a feature that lives in a library of its own
+shows that it left the other kernels alone (profiles/resample_isa_identical.txt, profiles/ddc_isa_identical.txt), and how
+a change that moves code between these files shows that no kernel changed (profiles/rs_shared_isa_identical.txt).  Used in
 round 5 to show that pruning the A/B alternates out of the roofline kernel changed no instruction of the kernels that
 ship (profiles/r05/a0_prune_isa_identical.txt); hipcc cross-compiles, no GPU needed."""
 import re
@@ -17,17 +19,18 @@ import tempfile
 from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
+COMPANIONS = ("navtex_amd/scan", "navtex_amd/resample", "navtex_amd/ddc")
 
 
 def compile_tree(tree: Path, out: Path, everything: bool = False) -> dict:
     csrc = tree / "navtex_amd" / "csrc"
     sources = [csrc / "nvx_cascade.hip"]
     if everything:
-        sources = sorted(csrc.glob("*.hip")) + sorted((tree / "navtex_amd" / "scan").glob("*.hip")) + sorted((tree / "navtex_amd" / "resample").glob("*.hip"))
+        sources = sorted(csrc.glob("*.hip")) + [src for d in COMPANIONS for src in sorted((tree / d).glob("*.hip"))]
     text = ""
     for src in sources:
         subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", f"-I{tree / 'include'}", f"-I{csrc}",
-                        f"-I{src.parent}", "--cuda-device-only", "-S", str(src), "-o", str(out)], check=True, capture_output=True)
+                        f"-I{src.parent}", f"-I{tree / 'navtex_amd' / 'resample'}", "--cuda-device-only", "-S", str(src), "-o", str(out)], check=True, capture_output=True)
         text += out.read_text()
     kernels = {}
     for sym in re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, flags=re.M):         # the kernels, not the data symbols
@@ -53,7 +56,7 @@ def main():
     with tempfile.TemporaryDirectory() as td:
         old = Path(td) / "old"
         old.mkdir()
-        extra = [d for d in ("navtex_amd/scan", "navtex_amd/resample") if everything and
+        extra = [d for d in COMPANIONS if everything and
                  subprocess.run(["git", "-C", str(ROOT), "cat-file", "-e", f"{rev}:{d}"], capture_output=True).returncode == 0]
         tar = subprocess.run(["git", "-C", str(ROOT), "archive", rev, "navtex_amd/csrc", *extra, "include"], check=True, capture_output=True).stdout
         subprocess.run(["tar", "x", "-C", str(old)], input=tar, check=True)
