@@ -1,7 +1,8 @@
 """Build helper: compiles libnavtex_amd.so (HIP kernels for gfx950 + host C/C++) and its
 companions libnavtex_amd_scan.so (the band scan, navtex_amd/scan/), libnavtex_amd_resample.so (the resampler,
-navtex_amd/resample/) and libnavtex_amd_ddc.so (the down-converter bank, navtex_amd/ddc/) in-tree with hipcc, and -- for
-tests only -- the oracle library and the compiled reference seams via oracle/Makefile.
+navtex_amd/resample/), libnavtex_amd_ddc.so (the down-converter bank, navtex_amd/ddc/) and libnavtex_amd_blank.so (the
+impulse noise blanker, navtex_amd/blank/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
+reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
     python navtex_amd/build.py --oracle   # + oracle (and reference seams when /root/reference exists)
@@ -45,6 +46,12 @@ DDC_LIB = PKG / "libnavtex_amd_ddc.so"
 DDC_HIP_SOURCES = ["nvx_ddc.hip"]
 DDC_CXX_SOURCES = ["nvx_ddc_host.cpp"]
 DDC_SHARED_C_SOURCES = ["nvx_resample_design.c"]           # of RESAMPLE
+# the fourth companion (include/navtex_amd_blank.h): its own sources; its kernel includes the resampler's nvx_rs_device.h for
+# the formats' loads and conversions, and links nothing of it
+BLANK = PKG / "blank"
+BLANK_LIB = PKG / "libnavtex_amd_blank.so"
+BLANK_HIP_SOURCES = ["nvx_blank.hip"]
+BLANK_CXX_SOURCES = ["nvx_blank_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp"]
 
@@ -107,6 +114,10 @@ def _ddc_jobs(hipcc: str, force: bool):
     return objs + [OBJ / (src + ".o") for src in DDC_SHARED_C_SOURCES], jobs
 
 
+def _blank_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, BLANK, [], BLANK_HIP_SOURCES, BLANK_CXX_SOURCES, also=(RESAMPLE,))
+
+
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
     # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
     tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
@@ -126,6 +137,8 @@ def build_lib(force: bool = False) -> Path:
     jobs += resample_jobs
     ddc_objs, ddc_jobs = _ddc_jobs(hipcc, force)
     jobs += ddc_jobs
+    blank_objs, blank_jobs = _blank_jobs(hipcc, force)
+    jobs += blank_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -152,6 +165,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, RESAMPLE_LIB, resample_objs, ["-lpthread", "-lm"])
     if force or _stale(DDC_LIB, ddc_objs):
         _link(hipcc, DDC_LIB, ddc_objs, ["-lpthread", "-lm"])
+    if force or _stale(BLANK_LIB, blank_objs):
+        _link(hipcc, BLANK_LIB, blank_objs, ["-lpthread"])
     return LIB
 
 
