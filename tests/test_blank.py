@@ -2,7 +2,10 @@
 argument safety, the launch arithmetic against 128-bit integers (a stand-alone program under ASan + UBSan), the restatement
 (tests/blank_ref.py) on cuts, clean signal, silence, the rails, the bypass, sustained loud input and the counters, and the
 acceptance case: a weak message under impulsive interference, decoded through the restatements with and without the
-blanker, at 252 kS/s and at 768 kS/s in front of the resampler."""
+blanker, at 252 kS/s and at 768 kS/s in front of the resampler; blank_streams (many rows at once) against blank() row by
+row; and the trap inputs of tests/test_gpu_blank_edges.py: each is shown to carry its feature on the restatement and to change
+words under a deliberately wrong variant of it (_variant: a ring of three, the three newest sums, the partial sum dropped at
+a chunk start, hold +- 1, >= for >, the reference not shifted)."""
 import ctypes as C
 import re
 import subprocess
@@ -266,3 +269,130 @@ def test_the_chain_at_768k_delivers_with_the_blanker_and_not_without(nv, bl, ora
     got = [bc.delivered(oracle, r, nv.FRAME_IN)[0] for r in (without, with_)]
     print("without", got[0] == [text], "with", got[1] == [text], "blanked", round(ref.blanked / ref.samples, 4))
     assert got[1] == [text] and got[0] != [text]
+
+
+# ------------------------------------------------------------------------------- the restatement for many rows at once
+@pytest.mark.parametrize("fmt", [br.CS16, br.CU8])
+def test_blank_streams_equals_blank_row_by_row(fmt):
+    rng = np.random.default_rng(fmt)
+    n, position = 9000, 2 ** 33 + 777
+    rows = rng.integers(-900, 901, size=(32, n, 2))
+    for s in range(32):
+        for at in rng.integers(0, n - 200, 6):
+            rows[s, at:at + int(rng.integers(1, 200))] = rng.integers(-30000, 30000, size=2)
+        rows[s, 5000 + s:5050 + 2 * s] = (30000, -30000)
+    rows = np.stack([rr.to_format(r.astype(np.int16), fmt, gain=3.0 if fmt == br.CU8 else 1.0) for r in rows])
+    for params in (dict(), dict(thr_q8=300, hold=1024, floor=0), dict(hold=0, floor=2000), dict(thr_q8=0)):
+        out, det, gone = br.blank_streams(rows, fmt, position=position, batch=5 * n, **params)
+        for s in range(32):
+            want, ref = br.blank(rows[s], fmt, position=position, **params)
+            assert np.array_equal(out[s], want) and (det[s], gone[s]) == (ref.detections, ref.blanked), (params, s)
+        assert (det > 0).all() or params.get("thr_q8") == 0
+
+
+# ------------------------------------------------------- the trap inputs of tests/test_gpu_blank_edges.py discriminate
+def _variant(x, fmt, thr_q8=br.THR_DEFAULT, hold=br.HOLD_DEFAULT, floor=br.FLOOR_DEFAULT, position=0, ring=4, need=4, hold_delta=0, ge=False,
+             shift=10, drop_at=()):
+    """The restatement once more in one shot, with a fault to choose: a ring of `ring` sums judged from `need` complete
+    blocks on, the hold off by hold_delta, >= for >, the reference not shifted, and the open block's sum in front of the
+    samples drop_at forgotten (what a chunk would see whose pre-roll lost the partial sum).  Returns int16 [n, 2]."""
+    c = rr.convert(x, fmt)
+    m = np.abs(c[:, 0]) + np.abs(c[:, 1])
+    idx = position + np.arange(len(c), dtype=np.int64)
+    b = idx // br.NB - position // br.NB
+    s = np.bincount(b, weights=m).astype(np.int64)
+    for at in drop_at:
+        lo = max((position // br.NB + int(b[at])) * br.NB - position, 0)
+        s[b[at]] -= int(m[lo:at].sum())
+    level = np.full(len(s), -1, dtype=np.int64)
+    for k in range(need, len(s)):
+        level[k] = max((thr_q8 * (int(s[k - ring:k].min()) >> shift)) >> 8, floor)
+    lv = level[b]
+    d = (lv >= 0) & ((m >= lv) if ge else (m > lv))
+    latest = np.maximum.accumulate(np.where(d, idx, np.int64(-1) << 40))
+    return np.where((idx - latest <= hold + hold_delta)[:, None], 0, c).astype(np.int16)
+
+
+RING_OF_THREE, THREE_NEWEST, NO_SHIFT, GE = dict(ring=3, need=3), dict(ring=3), dict(shift=0), dict(ge=True)
+
+
+@pytest.mark.parametrize("cell", range(len(br.form2_cells())))
+def test_form_2_trap_inputs_discriminate(cell):
+    """Case a's rows: the design's detections are the restatement's, every trap's feature is there, and each of the wrong
+    variants a pre-roll could amount to changes words."""
+    fmt, first, hold, _ = br.form2_cells()[cell]
+    rows, infos, slots = br.form2_trap_rows(fmt, first, hold, cell)
+    assert sorted(sl for ss in slots for sl in ss) == [0, 1, 2, 3]
+    for s in range(2):
+        x, info = rows[s], infos[s]
+        assert len(x) == first + 64 * 4096 + 5 + 3000 and info["starts"] == [first + 32 * 4096, first + 64 * 4096]
+        out, ref = br.blank(x, fmt, hold=hold)
+        assert np.array_equal(_variant(x, fmt, hold=hold), out)
+        assert np.array_equal(ref.d, info["det"]), "the detections are the designed ones and no other"
+        for C in info["starts"]:
+            assert ref.d[C - hold] and ref.gone[C] and not ref.gone[C + 1]                 # trap 1
+            assert not ref.d[C - hold - 1] and not ref.d[C - hold + 1:C + 2].any()       # no other whose hold ends at C or C + 1
+        assert ref.d[info["probes"]].all() and not ref.gone[info["quiet"]].any() and (len(info["quiet"]) == 4) == (info["off"] == 1023)
+        wrong = [dict(hold_delta=1)] + ([dict(hold_delta=-1)] if hold else []) + ([dict(drop_at=info["starts"])] if info["off"] < 1024 else [])
+        if 0 in slots[s]:                                      # the smallest sum in the oldest slot
+            wrong += [RING_OF_THREE, THREE_NEWEST]
+        for v in wrong:
+            got = _variant(x, fmt, hold=hold, **v)
+            assert not np.array_equal(got, out), v
+            if "hold_delta" in v:                              # ... at the chunk's first two samples
+                C = info["starts"][0]
+                assert not np.array_equal(got[C:C + 2], out[C:C + 2]), v
+            if "drop_at" in v and info["off"] == 1023:         # one sample's sum: only the probes at the level see it
+                q = info["quiet"]
+                assert not got[q].any() and out[q].any()
+
+
+@pytest.mark.parametrize("fmt", [br.CS16, br.CU8], ids=["cs16", "cu8"])
+def test_spike_inputs_discriminate(fmt):
+    """Case c's rows: as many detections as spikes, each blanking exactly hold + 1 samples; a hold one off changes words."""
+    x, at = br.spike_row(fmt, seed=3)
+    assert (at - br.SPIKE_FIRST - 4096 * (2 + np.arange(len(at)))).tolist() == br.spike_offsets(fmt) and len(at) == 16
+    assert at[br.spike_offsets(fmt).index(br.SPIKE_OFF)] % 1024 == 0 and at[br.spike_offsets(fmt).index(br.SPIKE_OFF - 1)] % 1024 == 1023
+    for hold in br.SPIKE_HOLDS:
+        out, ref = br.blank(x, fmt, hold=hold)
+        assert ref.detections == len(at) and ref.d[at].all() and ref.blanked == len(at) * (hold + 1)
+        for a in at:
+            assert ref.gone[a:a + hold + 1].all() and not ref.gone[a + hold + 1] and not ref.gone[a - 1]
+        assert np.array_equal(_variant(x, fmt, hold=hold), out)
+        for delta in (1, -1) if hold else (1,):
+            assert not np.array_equal(_variant(x, fmt, hold=hold, hold_delta=delta), out), (hold, delta)
+
+
+@pytest.mark.parametrize("position", br.LEVEL_POSITIONS)
+def test_level_inputs_discriminate(position):
+    """Case d's rows: a probe at the level is no detection and one a unit above it is; >= for >, an unshifted reference and
+    a ring that loses its oldest sum change words."""
+    for thr in br.LEVEL_THR:
+        for floor in br.LEVEL_FLOORS:
+            x, at_level, above = br.level_row(position, thr, floor, br.LEVEL_BLOCKS)
+            out, ref = br.blank(x, thr_q8=thr, hold=0, floor=floor, position=position)
+            assert len(above) >= 20 and ref.d[above].all() and not ref.d[at_level].any(), (thr, floor)
+            kw = dict(thr_q8=thr, hold=0, floor=floor, position=position)
+            assert np.array_equal(_variant(x, br.CS16, **kw), out)
+            for v in [GE] + ([NO_SHIFT, RING_OF_THREE, THREE_NEWEST] if floor <= 64 else []):
+                assert not np.array_equal(_variant(x, br.CS16, **kw, **v), out), (thr, floor, v)
+    # ref >> 10: the block of 1024 * 700 + 1023 gives the level of 700, the one of 1024 * 701 that of 701
+    x, at_level, _ = br.level_row(position, 256, 0, br.LEVEL_BLOCKS)
+    m = np.abs(x.astype(np.int64)).sum(axis=1)
+    assert {700, 701} <= set(m[at_level].tolist())
+    # four loud blocks, then passed
+    x, _, _ = br.level_row(position, 1024, 64, br.LEVEL_BLOCKS)
+    _, ref = br.blank(x, hold=0, position=position)
+    loud = [k for k, blk in enumerate(br.LEVEL_BLOCKS) if blk[0] == 20000]
+    per_block = [int(ref.d[k * 1024 - position % 1024:(k + 1) * 1024 - position % 1024].sum()) for k in loud]
+    assert per_block == [1024] * 4 + [0] * 2
+    # 2^28: five blocks at (-32768, -32768) from the reset on, thr_q8 = 4096: nothing in them, nothing in the quiet block behind
+    x, _, _ = br.level_row(position, 4096, 64, br.RAIL_BLOCKS)
+    _, ref = br.blank(x, thr_q8=4096, hold=0, position=position)
+    assert not ref.d[:6 * 1024 - position % 1024].any() and (x[:4096] == -32768).all()
+    assert br.level_of(1024 * 65536, 4096, 0) == 1 << 20 and 4096 * ((1024 * 65536) >> 10) == 1 << 28
+    # silence with floor = 0: every non-zero sample behind the first four blocks, and no zero one
+    x = br.silent_row(position)
+    _, ref = br.blank(x, hold=0, floor=0, position=position)
+    behind = np.arange(len(x)) >= 4 * 1024 - position % 1024
+    assert np.array_equal(ref.d, behind & x.any(axis=1)) and ref.detections > 200
