@@ -25,8 +25,8 @@
 // from nothing, storing and counting nothing: eight block ends later the ring, the partial sum and the detections of the
 // last block (hold reaches no further) are the stream's own.  The last chunk writes the other state row.
 // Integers only, except CF32's conversion.  The formats' sizes, load_sample and the CF32 rule are the resampler's
-// (nvx_rs_device.h).  Registers: DESIGN 3.9 says why the A-part bounds pass through an empty asm, why the detections are
-// bits, and why a wave's own values come back from the LDS.
+// (nvx_rs_device.h), and so are the tile's 16-byte loads (load_words).  Registers: DESIGN 3.9 says why the A-part bounds
+// pass through an empty asm, why the detections are bits, and why a wave's own values come back from the LDS.
 #include <type_traits>
 
 #include "nvx_blank_plan.h"
@@ -79,32 +79,6 @@ __device__ __forceinline__ uint32_t level_of(const uint32_t (&s)[4], uint32_t co
 
 // samples per lane and step, steps per region
 template <int FMT> struct Shape { static constexpr int SPT = (FMT == NVX_RS_CU8 || FMT == NVX_RS_CS8) ? 8 : 4, STEPS = NVX_BLANK_BLOCK / (64 * SPT); };
-
-// SPT samples from sample s (a multiple of SPT) of the row, as packed words
-template <int FMT>
-__device__ __forceinline__ void load_words(const char *row, int s, uint32_t *w)
-{
-    const u32x4 *p = (const u32x4 *)(row + (size_t)s * Fmt<FMT>::BPS);
-    if constexpr (FMT == NVX_RS_CS16) {
-        const u32x4 v = __builtin_nontemporal_load(p);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else if constexpr (FMT == NVX_RS_CU8 || FMT == NVX_RS_CS8) {
-        // a word holds I0 Q0 I1 Q1 as bytes: each becomes the high byte of its int16; (2u - 255) * 128 is (u << 8) ^ 0x8080
-        const uint32_t flip = FMT == NVX_RS_CU8 ? 0x80808080u : 0u;
-        const u32x4 v = __builtin_nontemporal_load(p);
-        const uint32_t d[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            // one v_perm_b32 each: selector 0 .. 3 names a byte of d, 0x0c is a zero byte
-            w[2 * k] = __builtin_amdgcn_perm(d[k], d[k], 0x010c000cu) ^ flip;
-            w[2 * k + 1] = __builtin_amdgcn_perm(d[k], d[k], 0x030c020cu) ^ flip;
-        }
-    } else {
-        const u32x4 v0 = __builtin_nontemporal_load(p), v1 = __builtin_nontemporal_load(p + 1);
-        w[0] = cf32_to_i16(v0.x) | (cf32_to_i16(v0.y) << 16); w[1] = cf32_to_i16(v0.z) | (cf32_to_i16(v0.w) << 16);
-        w[2] = cf32_to_i16(v1.x) | (cf32_to_i16(v1.y) << 16); w[3] = cf32_to_i16(v1.z) | (cf32_to_i16(v1.w) << 16);
-    }
-}
 
 template <int FMT>
 __global__ __launch_bounds__(NVX_BLANK_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void nvx_blank(const nvx_blank_args a)

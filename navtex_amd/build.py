@@ -1,7 +1,7 @@
 """Build helper: compiles libnavtex_amd.so (HIP kernels for gfx950 + host C/C++) and its
 companions libnavtex_amd_scan.so (the band scan, navtex_amd/scan/), libnavtex_amd_resample.so (the resampler,
-navtex_amd/resample/), libnavtex_amd_ddc.so (the down-converter bank, navtex_amd/ddc/) and libnavtex_amd_blank.so (the
-impulse noise blanker, navtex_amd/blank/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
+navtex_amd/resample/), libnavtex_amd_ddc.so (the down-converter bank, navtex_amd/ddc/), libnavtex_amd_blank.so (the
+impulse noise blanker, navtex_amd/blank/) and libnavtex_amd_iqc.so (the IQ corrector, navtex_amd/iqc/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
 reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
@@ -52,6 +52,11 @@ BLANK = PKG / "blank"
 BLANK_LIB = PKG / "libnavtex_amd_blank.so"
 BLANK_HIP_SOURCES = ["nvx_blank.hip"]
 BLANK_CXX_SOURCES = ["nvx_blank_host.cpp"]
+# the fifth companion (include/navtex_amd_iqc.h), built as the fourth is: nvx_rs_device.h again, and nothing linked
+IQC = PKG / "iqc"
+IQC_LIB = PKG / "libnavtex_amd_iqc.so"
+IQC_HIP_SOURCES = ["nvx_iqc.hip"]
+IQC_CXX_SOURCES = ["nvx_iqc_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp"]
 
@@ -118,6 +123,10 @@ def _blank_jobs(hipcc: str, force: bool):
     return _companion_jobs(hipcc, force, BLANK, [], BLANK_HIP_SOURCES, BLANK_CXX_SOURCES, also=(RESAMPLE,))
 
 
+def _iqc_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, IQC, [], IQC_HIP_SOURCES, IQC_CXX_SOURCES, also=(RESAMPLE,))
+
+
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
     # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
     tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
@@ -139,6 +148,8 @@ def build_lib(force: bool = False) -> Path:
     jobs += ddc_jobs
     blank_objs, blank_jobs = _blank_jobs(hipcc, force)
     jobs += blank_jobs
+    iqc_objs, iqc_jobs = _iqc_jobs(hipcc, force)
+    jobs += iqc_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -167,6 +178,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, DDC_LIB, ddc_objs, ["-lpthread", "-lm"])
     if force or _stale(BLANK_LIB, blank_objs):
         _link(hipcc, BLANK_LIB, blank_objs, ["-lpthread"])
+    if force or _stale(IQC_LIB, iqc_objs):
+        _link(hipcc, IQC_LIB, iqc_objs, ["-lpthread"])
     return LIB
 
 

@@ -1,5 +1,6 @@
-// nvx_rs_device.h -- what the kernels of the resampler (nvx_resample.hip) and of the down-converter bank
-// (navtex_amd/ddc/nvx_ddc.hip) have word for word in common: the vector types, the small arithmetic, the formats'
+// nvx_rs_device.h -- what the kernels of the resampler (nvx_resample.hip), of the down-converter bank
+// (navtex_amd/ddc/nvx_ddc.hip), of the blanker (navtex_amd/blank/nvx_blank.hip) and of the IQ corrector
+// (navtex_amd/iqc/nvx_iqc.hip) have word for word in common: the vector types, the small arithmetic, the formats'
 // conversions, and the launch of a kernel family's eight instances.  Internal; each library compiles its own copy.  The
 // kernel bodies stay in their files: see DESIGN 3.8.
 #ifndef NVX_RS_DEVICE_H
@@ -110,6 +111,40 @@ __device__ __forceinline__ void convert_group(const u32x4 (&v)[Fmt<FMT>::NV], u3
         }
         I.x = i[0]; I.y = i[1]; I.z = i[2]; I.w = i[3];
         Q.x = q[0]; Q.y = q[1]; Q.z = q[2]; Q.w = q[3];
+    }
+}
+
+template <bool NONTEMPORAL>
+__device__ __forceinline__ u32x4 rs_load16(const u32x4 *p)
+{
+    if constexpr (NONTEMPORAL) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+
+// the 4 (CS16, CF32) or 8 (CU8, CS8) samples from sample s (a multiple of that) of the row, as packed words: one 16-byte load,
+// two for CF32.  NONTEMPORAL as in load_group (the blanker reads once; the IQ corrector's first pass leaves the lines cached)
+template <int FMT, bool NONTEMPORAL = true>
+__device__ __forceinline__ void load_words(const char *row, int s, uint32_t *w)
+{
+    const u32x4 *p = (const u32x4 *)(row + (size_t)s * Fmt<FMT>::BPS);
+    if constexpr (FMT == NVX_RS_CS16) {
+        const u32x4 v = rs_load16<NONTEMPORAL>(p);
+        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else if constexpr (FMT == NVX_RS_CU8 || FMT == NVX_RS_CS8) {
+        // a word holds I0 Q0 I1 Q1 as bytes: each becomes the high byte of its int16; (2u - 255) * 128 is (u << 8) ^ 0x8080
+        const uint32_t flip = FMT == NVX_RS_CU8 ? 0x80808080u : 0u;
+        const u32x4 v = rs_load16<NONTEMPORAL>(p);
+        const uint32_t d[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            // one v_perm_b32 each: selector 0 .. 3 names a byte of d, 0x0c is a zero byte
+            w[2 * k] = __builtin_amdgcn_perm(d[k], d[k], 0x010c000cu) ^ flip;
+            w[2 * k + 1] = __builtin_amdgcn_perm(d[k], d[k], 0x030c020cu) ^ flip;
+        }
+    } else {
+        const u32x4 v0 = rs_load16<NONTEMPORAL>(p), v1 = rs_load16<NONTEMPORAL>(p + 1);
+        w[0] = cf32_to_i16(v0.x) | (cf32_to_i16(v0.y) << 16); w[1] = cf32_to_i16(v0.z) | (cf32_to_i16(v0.w) << 16);
+        w[2] = cf32_to_i16(v1.x) | (cf32_to_i16(v1.y) << 16); w[3] = cf32_to_i16(v1.z) | (cf32_to_i16(v1.w) << 16);
     }
 }
 
