@@ -1,8 +1,9 @@
 """Build helper: compiles libnavtex_amd.so (HIP kernels for gfx950 + host C/C++) and its
 companions libnavtex_amd_scan.so (the band scan, navtex_amd/scan/), libnavtex_amd_resample.so (the resampler,
 navtex_amd/resample/), libnavtex_amd_ddc.so (the down-converter bank, navtex_amd/ddc/), libnavtex_amd_blank.so (the
-impulse noise blanker, navtex_amd/blank/), libnavtex_amd_iqc.so (the IQ corrector, navtex_amd/iqc/) and libnavtex_amd_real.so
-(the real-input converter, navtex_amd/real/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
+impulse noise blanker, navtex_amd/blank/), libnavtex_amd_iqc.so (the IQ corrector, navtex_amd/iqc/), libnavtex_amd_real.so
+(the real-input converter, navtex_amd/real/) and libnavtex_amd_narrow.so (the narrowband interpolator, navtex_amd/narrow/)
+in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
 reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
@@ -63,6 +64,12 @@ REAL = PKG / "real"
 REAL_LIB = PKG / "libnavtex_amd_real.so"
 REAL_HIP_SOURCES = ["nvx_real.hip"]
 REAL_CXX_SOURCES = ["nvx_real_host.cpp"]
+# the seventh companion (include/navtex_amd_narrow.h): its own design, kernel and host side; nvx_rs_device.h once more
+NARROW = PKG / "narrow"
+NARROW_LIB = PKG / "libnavtex_amd_narrow.so"
+NARROW_C_SOURCES = ["nvx_narrow_design.c"]
+NARROW_HIP_SOURCES = ["nvx_narrow.hip"]
+NARROW_CXX_SOURCES = ["nvx_narrow_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp"]
 
@@ -137,6 +144,10 @@ def _real_jobs(hipcc: str, force: bool):
     return _companion_jobs(hipcc, force, REAL, [], REAL_HIP_SOURCES, REAL_CXX_SOURCES, also=(RESAMPLE,))
 
 
+def _narrow_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, NARROW, NARROW_C_SOURCES, NARROW_HIP_SOURCES, NARROW_CXX_SOURCES, also=(RESAMPLE,))
+
+
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
     # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
     tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
@@ -162,6 +173,8 @@ def build_lib(force: bool = False) -> Path:
     jobs += iqc_jobs
     real_objs, real_jobs = _real_jobs(hipcc, force)
     jobs += real_jobs
+    narrow_objs, narrow_jobs = _narrow_jobs(hipcc, force)
+    jobs += narrow_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -194,6 +207,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, IQC_LIB, iqc_objs, ["-lpthread"])
     if force or _stale(REAL_LIB, real_objs):
         _link(hipcc, REAL_LIB, real_objs, ["-lpthread"])
+    if force or _stale(NARROW_LIB, narrow_objs):
+        _link(hipcc, NARROW_LIB, narrow_objs, ["-lpthread", "-lm"])
     return LIB
 
 
