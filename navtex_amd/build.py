@@ -2,8 +2,8 @@
 companions libnavtex_amd_scan.so (the band scan, navtex_amd/scan/), libnavtex_amd_resample.so (the resampler,
 navtex_amd/resample/), libnavtex_amd_ddc.so (the down-converter bank, navtex_amd/ddc/), libnavtex_amd_blank.so (the
 impulse noise blanker, navtex_amd/blank/), libnavtex_amd_iqc.so (the IQ corrector, navtex_amd/iqc/), libnavtex_amd_real.so
-(the real-input converter, navtex_amd/real/) and libnavtex_amd_narrow.so (the narrowband interpolator, navtex_amd/narrow/)
-in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
+(the real-input converter, navtex_amd/real/), libnavtex_amd_narrow.so (the narrowband interpolator, navtex_amd/narrow/) and
+libnavtex_amd_tap.so (the channel tap, navtex_amd/tap/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
 reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
@@ -70,6 +70,12 @@ NARROW_LIB = PKG / "libnavtex_amd_narrow.so"
 NARROW_C_SOURCES = ["nvx_narrow_design.c"]
 NARROW_HIP_SOURCES = ["nvx_narrow.hip"]
 NARROW_CXX_SOURCES = ["nvx_narrow_host.cpp"]
+# the eighth companion (include/navtex_amd_tap.h), built as the seventh is; it also reads the bank's table header nvx_ddc_table.h
+TAP = PKG / "tap"
+TAP_LIB = PKG / "libnavtex_amd_tap.so"
+TAP_C_SOURCES = ["nvx_tap_design.c"]
+TAP_HIP_SOURCES = ["nvx_tap.hip"]
+TAP_CXX_SOURCES = ["nvx_tap_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp"]
 
@@ -148,6 +154,10 @@ def _narrow_jobs(hipcc: str, force: bool):
     return _companion_jobs(hipcc, force, NARROW, NARROW_C_SOURCES, NARROW_HIP_SOURCES, NARROW_CXX_SOURCES, also=(RESAMPLE,))
 
 
+def _tap_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, TAP, TAP_C_SOURCES, TAP_HIP_SOURCES, TAP_CXX_SOURCES, also=(RESAMPLE, DDC))
+
+
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
     # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
     tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
@@ -175,6 +185,8 @@ def build_lib(force: bool = False) -> Path:
     jobs += real_jobs
     narrow_objs, narrow_jobs = _narrow_jobs(hipcc, force)
     jobs += narrow_jobs
+    tap_objs, tap_jobs = _tap_jobs(hipcc, force)
+    jobs += tap_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -209,6 +221,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, REAL_LIB, real_objs, ["-lpthread"])
     if force or _stale(NARROW_LIB, narrow_objs):
         _link(hipcc, NARROW_LIB, narrow_objs, ["-lpthread", "-lm"])
+    if force or _stale(TAP_LIB, tap_objs):
+        _link(hipcc, TAP_LIB, tap_objs, ["-lpthread", "-lm"])
     return LIB
 
 
