@@ -1,8 +1,10 @@
 """The IQ corrector (include/navtex_amd_iqc.h) on the GPU (-m gpu): output words equal to the restatement (tests/iqc_ref.py)
-for every format and window, calls cut anywhere against one shot, a reset stream rejoining the others, the rails and
-full-scale random input (float32 specials) with the counters and the window's sums, the rejection reasons, the two launch
-shapes, positions beyond 2^32, set / HOLD / TRACK between calls, push against resident, and the acceptance case's seed 11
-through a two-chain handle.  Every comparison is ==, with sentinels around every output row."""
+for every format and window in one call from position 0, W = 4 cut into calls at and next to the block ends against one shot,
+a reset stream rejoining the others, the rails and full-scale random input (float32 specials) with the counters and the
+window's sums, the rejection reasons 1, 2 and 4, the two launch shapes, positions beyond 2^32, set / HOLD / TRACK between calls,
+push against resident, and the acceptance case's seed 11 through a two-chain handle.  Every comparison is ==, with sentinels
+around every output row.  Where a block ends inside a tile, the longer windows across calls, form 2 beyond its one case here,
+the apply at the limits of nvx_iqc_set and reason 3: tests/test_gpu_iqc_edges.py."""
 from pathlib import Path
 
 import numpy as np
@@ -11,6 +13,7 @@ import pytest
 import iqc_cases as ic
 import iqc_ref as ir
 import resample_ref as rr
+from iqc_cases import _extremes
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -141,28 +144,6 @@ def test_one_shot_equals_calls_cut_at_the_block_ends_and_a_reset_stream_rejoins(
 
 
 # ------------------------------------------------------------------------------------------------------------------ (c)
-def _extremes(fmt, n, seed):
-    """Three rows in format fmt: every sample at the lowest value, the rails alternating in sign, and full-scale random."""
-    dt = rr.DTYPES[fmt]
-    rng = np.random.default_rng(seed)
-    if fmt == ir.CF32:
-        lo, hi = np.float32(-1.0), np.float32(32767.0 / 32768.0)
-        rnd = rng.uniform(-1.3, 1.3, size=(n, 2)).astype(np.float32)
-        special = np.array([np.nan, np.inf, -np.inf, 1e-42, -1e-42, 0.5 / 32768, 1.5 / 32768, 2.5 / 32768, -0.5 / 32768, -1.5 / 32768,
-                            32766.5 / 32768, 32767.5 / 32768, -32768.5 / 32768, 1.0, -1.0, 3e38, -3e38, 0.0, -0.0, 123.5 / 32768], dtype=np.float32)
-        at = rng.integers(0, n, size=(400, 2))
-        rnd[at[:, 0], at[:, 1] % 2] = special[rng.integers(0, len(special), size=400)]
-        rnd[:len(special), 0] = special
-    else:
-        lo, hi = np.iinfo(dt).min, np.iinfo(dt).max
-        rnd = rng.integers(int(lo), int(hi) + 1, size=(n, 2)).astype(dt)
-    low = np.full((n, 2), lo, dtype=dt)
-    alt = low.copy()
-    alt[1::2, 0] = hi
-    alt[(np.arange(n) // 3) % 2 == 1, 1] = hi
-    return [low, alt, rnd]
-
-
 @pytest.mark.parametrize("fmt", FORMATS, ids=FORMAT_IDS)
 def test_the_rails_and_full_scale_random_input_with_counters_and_sums(nv, iq, fmt):
     """Every product at its largest: I^2 + Q^2 = 2^31 and 2 I Q = 2^31 in every sample of the first row.  The counters and the

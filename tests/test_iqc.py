@@ -1,6 +1,7 @@
 """The IQ corrector (include/navtex_amd_iqc.h) on the CPU: the header and the companion library's exports and argument
 safety, the launch arithmetic against 128-bit integers (a stand-alone program under ASan + UBSan), the restatement
-(tests/iqc_ref.py) on cuts at the block ends, the identity, the rejection reasons and the rails, and end to end through the
+(tests/iqc_ref.py) on cuts at the block ends, the identity, the four rejection reasons and the rails, the cut plan of the GPU
+suite's block-end sweep (tests/test_gpu_iqc_edges.py) against a model of the kernels' tiles, and end to end through the
 oracle: the acceptance case (a weak 490 station under the image of a strong 518 one, twelve seeds), the image of a tone
 before and behind the corrector, and the known limit -- two strong stations at mirrored frequencies."""
 import ctypes as C
@@ -201,6 +202,75 @@ def test_the_rejection_reasons_two_and_four():
     # unrotated, three times the level is reason 2: the coherence comes first
     i = x[:, 0]
     assert ir.correct(np.stack([i, 3 * (i // 3)], axis=1).astype(np.int16), ir.CS16, 2)[1].reason == 2
+
+
+def test_reason_three_what_is_left_of_q_is_not_positive():
+    """I = 5 i, Q = i: a = -1/5 passes step 7, and v = CQQ + 2 a CIQ + a^2 CII is nothing but rounding: reason 3, the identity
+    gain, the offset removed all the same."""
+    n = 5 * B + 100
+    x = ic.q_fifth_of_i(n, 63)
+    out, ref = ir.correct(x, ir.CS16, 2)
+    assert ref.reason == 3 and ref.rejected == 2 and ref.solved == 0 and ref.coef[2:] == (0, 16384)
+    assert [h[2] for h in ref.history] == [3, 3]
+    dI, dQ = ref.history[0][1][:2]
+    assert np.array_equal(out[4 * B:5 * B], x[4 * B:5 * B].astype(np.int64) - (dI, dQ)) and np.array_equal(out[:4 * B], x[:4 * B])
+    for y in (x * (1, -1), np.stack([8 * (x[:, 1] // 2), x[:, 1] // 2], axis=1)):            # Q = -i; I = 8 i
+        assert ir.correct(y.astype(np.int16), ir.CS16, 2)[1].reason == 3
+    assert ir.correct(ic.q_fifth_of_i(17 * B + 100, 63), ir.CS16, 4)[1].history[-1][2] == 3
+
+
+# ------------------------------------------------------------------------------------ the block-end sweep's cut plan
+def test_the_tile_model_against_the_blocks_sample_by_sample():
+    """iqc_cases.block_ends_in_tiles against the header's definition taken literally: sample k of a call at `position` lies
+    in block (position + k) div 65 536 and in tile k div 4096."""
+    rng = np.random.default_rng(8)
+    cases = [(0, 5 * B), (B - 1, 2), (B - 1, 1), (B - 4096, 4096), (B - 4096, 4097), (B - 4095, 4096), (2 ** 40 + 5, 3 * B), (7, B - 7), (7, B - 6)]
+    cases += [(int(rng.integers(0, 2 ** 41)), int(rng.integers(1, 3 * B))) for _ in range(40)]
+    for position, n_in in cases:
+        k = np.arange(n_in, dtype=np.int64)
+        block, tile = (position + k) // B, k // 4096
+        want = []
+        for t in np.unique(tile[1:][block[1:] != block[:-1]]):       # the tiles in which a sample is the first of its block ...
+            mine = block[tile == t]
+            if mine[0] != mine[-1]:                                  # ... and not the tile's first
+                want.append((int((mine == mine[0]).sum()), int((tile == t).sum()) == 4096))
+        assert ic.block_ends_in_tiles(position, n_in) == want, (position, n_in)
+    assert ic.block_ends_in_tiles(B - 100, 200) == [(100, False)] and ic.block_ends_in_tiles(B - 100, 100) == []
+
+
+def test_the_sweeps_cut_plan_reaches_every_block_end_and_both_call_ends():
+    cuts = ic.sweep_cuts()
+    splits, ragged, exact = ic.sweep_coverage(cuts)
+    assert min(cuts) > 0 and len(cuts) == 44 and sum(cuts) == 35 * B + 777
+    assert set(splits) >= set(ic.SWEEP_N_A) and len(ic.SWEEP_N_A) == 24
+    # the call ends 1, 5 or 90 samples behind the block's end, in the same tile: on the edge of a lane's group, and inside one
+    assert sorted(ragged) == sorted(ic.SWEEP_SHORT) and len(ragged) >= 5 and {ic.SWEEP_SHORT[n_a] for n_a in ragged} == {1, 5, 90}
+    assert {(n_a + ic.SWEEP_SHORT[n_a]) % 8 == 0 for n_a in ragged} == {True, False}
+    # the call ends on the block's end, and the next one starts a block
+    assert exact == len(ic.SWEEP_EXACT) >= 5
+    # from block 5 on every block's end is aimed at: it lies in the first three tiles of a call, or is the call's end
+    pos, aimed = 0, set()
+    for cut in cuts:
+        for e in range(pos // B + 1, (pos + cut) // B + 1):
+            if e * B - pos < 3 * 4096 or e * B == pos + cut:
+                aimed.add(e)
+        pos += cut
+    assert aimed == set(range(ic.SWEEP_FIRST_END, 35))
+
+
+@pytest.mark.parametrize("fmt", [ir.CS16, ir.CU8, ir.CS8, ir.CF32])
+def test_the_restatement_in_the_sweeps_cuts_equals_one_shot(fmt):
+    cuts = ic.sweep_cuts()
+    for x in ic.sweep_rows(fmt):
+        one, ref = ir.correct(x, fmt, 2)
+        coefs = [h[1] for h in ref.history]
+        assert ref.solved == 32 and ref.rejected == 0 and all(a != b for a, b in zip(coefs, coefs[1:]))
+        c = ir.Corrector(fmt, 2)
+        pos, parts = 0, []
+        for cut in cuts:
+            parts.append(c.push(x[pos:pos + cut])); pos += cut
+        assert pos == len(x) and np.array_equal(np.concatenate(parts), one)
+        assert (c.coef, c.reason, c.sums(), c.samples, c.solved, c.rejected, c.history) == (ref.coef, ref.reason, ref.sums(), len(x), 32, 0, ref.history)
 
 
 def test_the_rails():
