@@ -366,7 +366,9 @@ NVX_API size_t nvx_bit_count(nvx_handle *h, int stream, int chain);
  * which = 0 FIR cascade (wideband handles: the fused channeliser + cascade
  * kernel), 1 demodulator, 2 FIR3 as its own kernel (wideband handles, whose
  * fused kernel ends at FIR2; 0 otherwise), 3 the demodulator's sequential
- * kernel alone (part of 1).  Valid after a synchronise.                      */
+ * kernel alone (part of 1), 4 the update kernel of automatic frequency
+ * control (navtex_amd_afc.h; 0 while no chain tracks).  Valid after a
+ * synchronise.                                                              */
 NVX_API float nvx_last_kernel_ms(nvx_handle *h, int which);
 NVX_API void  nvx_enable_timing(nvx_handle *h, int enabled);
 /* sum of the event durations (ms) and number of timed launches collected since

@@ -19,6 +19,9 @@
  *   shift_hz   = b_hz - y_hz                             (NAVTEX: positive, somewhat below 170: transitions pull inward)
  *   eye_snr_db = 10 log10(((muB - muY) / 2)^2 / ((varB + varY) / 2)), population variances of phi, clamped at 0
  *   contrast   = (sum_mf_hi - sum_mf_lo) / (sum_mf_hi + sum_mf_lo), in [0, 1]
+ *
+ * A chain under automatic frequency control (navtex_amd_afc.h) is measured launch by launch, each launch against the k
+ * that launch ran with: its offset_hz is what the loop has not removed yet, not the carrier's distance from the centre.
  */
 #ifndef NAVTEX_AMD_SIGNAL_H
 #define NAVTEX_AMD_SIGNAL_H

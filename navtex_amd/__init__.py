@@ -151,6 +151,44 @@ def channelise_time_stats(reset: bool = False):
     return s.value, n.value
 
 
+def afc_config(**fields) -> N.AfcConfig:
+    """nvx_afc_config at its defaults (nvx_afc_config_default) with `fields` set: gain_shift, max_step, range_k, min_samples,
+    contrast_min (include/navtex_amd_afc.h)."""
+    c = N.AfcConfig()
+    lib.nvx_afc_config_default(C.byref(c))
+    for k, v in fields.items():
+        if k not in dict(N.AfcConfig._fields_):
+            raise TypeError(f"nvx_afc_config has no field {k}")
+        setattr(c, k, v)
+    return c
+
+
+def _afc_enable(fn, h, stream, chain, cfg, fields, where) -> None:
+    if fields:                                           # on top of the defaults, or of a copy of the caller's cfg
+        base = cfg
+        cfg = afc_config(**fields)
+        if base is not None:
+            cfg = N.AfcConfig.from_buffer_copy(base)
+            for k, v in fields.items():
+                setattr(cfg, k, v)
+    N.check(fn(h, stream, chain, C.byref(cfg) if cfg is not None else None), where)
+
+
+def _afc_status(fn, h, stream, chain, where) -> dict:
+    st = N.AfcStatus()
+    N.check(fn(h, stream, chain, C.byref(st)), where)
+    return {f: getattr(st, f) for f, _ in N.AfcStatus._fields_}
+
+
+def _afc_trace(fn, h, stream, chain, where) -> List[int]:
+    out, buf = [], (C.c_int32 * N.AFC_TRACE_KEEP)()
+    while True:
+        n = N.check(fn(h, stream, chain, buf, N.AFC_TRACE_KEEP), where)
+        out += buf[:n]
+        if n < N.AFC_TRACE_KEEP:
+            return out
+
+
 # ------------------------------------------------------------------ pipeline
 class HandleStats:
     """Instrumentation of one nvx_handle (self._h): what a Pipeline offers about itself and what a Group offers about each
@@ -236,6 +274,23 @@ class HandleStats:
         off, ref = C.c_double(), C.c_int()
         N.check(lib.nvx_get_carrier(self._h, stream, chain, C.byref(off), C.byref(ref)), "nvx_get_carrier")
         return off.value, bool(ref.value)
+
+    def afc_enable(self, stream: int, chain: int, cfg: Optional[N.AfcConfig] = None, **fields) -> None:
+        """Track (stream, chain)'s carrier about its centre on the GPU (nvx_afc_enable, include/navtex_amd_afc.h): cfg, or the
+        defaults, with `fields` set on top of either (afc_config names them)."""
+        _afc_enable(lib.nvx_afc_enable, self._h, stream, chain, cfg, fields, "nvx_afc_enable")
+
+    def afc_disable(self, stream: int, chain: int, keep: bool = False) -> None:
+        """Stop tracking (nvx_afc_disable); keep: the tracked k becomes the chain's carrier."""
+        N.check(lib.nvx_afc_disable(self._h, stream, chain, int(keep)), "nvx_afc_disable")
+
+    def afc_status(self, stream: int, chain: int) -> dict:
+        """Every field of nvx_afc_status (nvx_afc_read)."""
+        return _afc_status(lib.nvx_afc_read, self._h, stream, chain, "nvx_afc_read")
+
+    def afc_trace(self, stream: int, chain: int) -> List[int]:
+        """The k each collected launch ran with since the previous call (nvx_afc_trace), oldest first."""
+        return _afc_trace(lib.nvx_afc_trace, self._h, stream, chain, "nvx_afc_trace")
 
     def set_forms(self, independent: int = -1, dynamic_preroll: int = -1, demod_tiles: int = -1) -> None:
         """Force the kernel forms of the launches from here on (nvx_debug_set_forms): each -1 = automatic, 0 / 1 = off / on."""
@@ -540,6 +595,19 @@ class Group:
         applied = C.c_double()
         N.check(lib.nvx_group_set_carrier(self._g, stream, chain, float(offset_hz), C.byref(applied)), "nvx_group_set_carrier")
         return applied.value
+
+    def afc_enable(self, stream: int, chain: int, cfg: Optional[N.AfcConfig] = None, **fields) -> None:
+        """nvx_group_afc_enable: HandleStats.afc_enable of the member that owns global stream `stream`."""
+        _afc_enable(lib.nvx_group_afc_enable, self._g, stream, chain, cfg, fields, "nvx_group_afc_enable")
+
+    def afc_disable(self, stream: int, chain: int, keep: bool = False) -> None:
+        N.check(lib.nvx_group_afc_disable(self._g, stream, chain, int(keep)), "nvx_group_afc_disable")
+
+    def afc_status(self, stream: int, chain: int) -> dict:
+        return _afc_status(lib.nvx_group_afc_read, self._g, stream, chain, "nvx_group_afc_read")
+
+    def afc_trace(self, stream: int, chain: int) -> List[int]:
+        return _afc_trace(lib.nvx_group_afc_trace, self._g, stream, chain, "nvx_group_afc_trace")
 
     def carrier(self, stream: int, chain: int) -> Tuple[float, bool]:
         """(offset in Hz, runs the reference mixer) of global stream `stream`'s chain -- nvx_group_get_carrier."""

@@ -58,6 +58,21 @@ class SignalReport(C.Structure):
         "power_db", "b_hz", "y_hz", "offset_hz", "shift_hz", "eye_snr_db", "contrast")]
 
 
+class AfcConfig(C.Structure):
+    """nvx_afc_config (include/navtex_amd_afc.h)."""
+    _fields_ = [("struct_size", C.c_uint32), ("gain_shift", C.c_int), ("max_step", C.c_int), ("range_k", C.c_int),
+                ("min_samples", C.c_int), ("contrast_min", C.c_double)]
+
+
+class AfcStatus(C.Structure):
+    """nvx_afc_status (include/navtex_amd_afc.h)."""
+    _fields_ = [("enabled", C.c_int), ("centre_k", C.c_int), ("k_last", C.c_int), ("last_step", C.c_int), ("offset_hz", C.c_double),
+                ("launches", C.c_uint64), ("updates", C.c_uint64), ("held", C.c_uint64), ("clamped", C.c_uint64)]
+
+
+AFC_TRACE_KEEP = 1024                                                                # include/navtex_amd_afc.h
+
+
 def _load() -> C.CDLL:
     if not _LIB_PATH.exists():
         raise ImportError(
@@ -113,6 +128,12 @@ def _load() -> C.CDLL:
         "nvx_get_carrier": (i, [vp, i, i, C.POINTER(C.c_double), C.POINTER(i)]),
         "nvx_group_set_carrier": (i, [vp, i, i, C.c_double, C.POINTER(C.c_double)]),
         "nvx_group_get_carrier": (i, [vp, i, i, C.POINTER(C.c_double), C.POINTER(i)]),
+        "nvx_afc_config_default": (None, [C.POINTER(AfcConfig)]),
+        "nvx_afc_enable": (i, [vp, i, i, C.POINTER(AfcConfig)]), "nvx_afc_disable": (i, [vp, i, i, i]),
+        "nvx_afc_read": (i, [vp, i, i, C.POINTER(AfcStatus)]), "nvx_afc_trace": (i, [vp, i, i, C.POINTER(C.c_int32), sz]),
+        "nvx_group_afc_enable": (i, [vp, i, i, C.POINTER(AfcConfig)]), "nvx_group_afc_disable": (i, [vp, i, i, i]),
+        "nvx_group_afc_read": (i, [vp, i, i, C.POINTER(AfcStatus)]), "nvx_group_afc_trace": (i, [vp, i, i, C.POINTER(C.c_int32), sz]),
+        "nvx_afc_step_host": (i, [i, i, i, i, C.c_double, i, i, i, C.c_uint, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_uint)]),
         "nvx_device_count": (i, []), "nvx_device_alloc": (vp, [i, sz]), "nvx_device_free": (None, [i, vp]),
         "nvx_memcpy_h2d": (i, [i, vp, vp, sz]), "nvx_memcpy_d2h": (i, [i, vp, vp, sz]), "nvx_device_sync": (i, [i]),
         "nvx_stream_create": (vp, [i]), "nvx_stream_destroy": (None, [i, vp]),

@@ -77,7 +77,11 @@ TAP_C_SOURCES = ["nvx_tap_design.c"]
 TAP_HIP_SOURCES = ["nvx_tap.hip"]
 TAP_CXX_SOURCES = ["nvx_tap_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
-               "nvx_tune.cpp"]
+               "nvx_tune.cpp", "nvx_afc.cpp"]
+# automatic frequency control (include/navtex_amd_afc.h): its update kernel is part of libnavtex_amd.so, in a directory of
+# its own beside csrc (the law it runs, csrc/nvx_afc_law.h, is shared with the host)
+AFC = PKG / "afc"
+AFC_HIP_SOURCES = ["nvx_afc.hip"]
 
 # -ffp-contract=off is part of the numerical contract: FIR products and sums are
 # rounded separately, exactly as the reference's x86-64 build does.
@@ -197,6 +201,11 @@ def build_lib(force: bool = False) -> Path:
         if force or _stale(o, [CSRC / src] + headers):
             jobs.append([hipcc, f"--offload-arch={ARCH}", "-std=c++17", *COMMON, "-c", CSRC / src, "-o", o])
         objs.append(o)
+    for src in AFC_HIP_SOURCES:
+        o = OBJ / (src + ".o")
+        if force or _stale(o, [AFC / src] + headers):
+            jobs.append([hipcc, f"--offload-arch={ARCH}", "-std=c++17", *COMMON, "-c", AFC / src, "-o", o])
+        objs.append(o)
     for src in CXX_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -245,6 +254,7 @@ def build_variant(name: str, flags, sources=("nvx_cascade.hip", "nvx_wideband_fu
             objs.append(o)
         else:
             objs.append(OBJ / (src + ".o"))
+    objs += [OBJ / (src + ".o") for src in AFC_HIP_SOURCES]
     from concurrent.futures import ThreadPoolExecutor
     with ThreadPoolExecutor(max_workers=2) as pool:
         list(pool.map(_run, jobs))

@@ -9,10 +9,16 @@
 #include "nvx_handle.h"
 #include <chrono>
 #include <cmath>
+#include "navtex_amd_afc.h"
 #include "navtex_amd_signal.h"
 #include "navtex_amd_soft.h"
 #include "navtex_amd_tune.h"
 #include "nvx_fsm.h"
+
+// (nvx_kernels.h) weak: the host runtime links without the kernels too, and tracking cannot be enabled then
+extern "C" hipError_t nvx_launch_afc_update(const nvx_afc_args *a, hipStream_t s) __attribute__((weak));
+static_assert(NVX_AFC_LAW_C == NVX_AFC_C && NVX_AFC_K_MAX * NVX_TUNE_STEP_HZ == NVX_TUNE_MAX_HZ, "the law's constants are the header's");
+static_assert(sizeof(nvx_afc_note) == 8 && sizeof(nvx_afc_par) == 32, "layouts of nvx_afc_law.h");
 
 // ------------------------------------------------------------------ errors
 static thread_local char g_err[512] = "";
@@ -107,17 +113,60 @@ static void free_debug(nvx_handle *h)
     for (double **p : { &h->d_dphi, &h->d_corr, &h->d_csum }) { (void)hipFree(*p); *p = nullptr; }
 }
 
-// nvx_enable_signal_report's buffers, made together and released together; what the reports had summed goes with them
-static void free_signal(nvx_handle *h)
+// The signal sums' buffers, made together and released together: the user's reports (nvx_enable_signal_report) and
+// automatic frequency control (nvx_afc_enable) both need them
+static void free_signal_buffers(nvx_handle *h)
 {
     (void)hipFree(h->d_sig_part); h->d_sig_part = nullptr;
     for (auto &r : h->res) {
         (void)hipFree(r.d_sig); r.d_sig = nullptr;
         (void)hipHostFree(r.h_sig); r.h_sig = nullptr;
-        r.sig = false;                                   // (a launch still to be collected brings no records any more)
     }
+    h->sig_stride = 0;
+}
+
+static int make_signal_buffers(nvx_handle *h, const char *who)
+{
+    if (h->d_sig_part) return NVX_OK;
+    // partials per slot: one, or (the tile-parallel front) the head's and one per tile from the third on
+    const int tiles = (h->y3_cap + NVX_FRONT_TILE - 1) / NVX_FRONT_TILE;
+    const int stride = std::max(1, tiles - 1);
+    const size_t rec = (size_t)h->n_slots * sizeof(nvx_sig_rec);
+    hipError_t e = hipMalloc(&h->d_sig_part, rec * (size_t)stride);
+    if (e != hipSuccess) h->d_sig_part = nullptr;
+    for (auto &r : h->res) {
+        if (e == hipSuccess) e = hipMalloc(&r.d_sig, rec);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&r.h_sig, rec, hipHostMallocDefault);
+    }
+    if (e != hipSuccess) {
+        free_signal_buffers(h);
+        nvx_set_error("%s: allocation failed: %s", who, hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? NVX_ERR_NOMEM : NVX_ERR_HIP;
+    }
+    h->sig_stride = stride;
+    return NVX_OK;
+}
+
+// the user's reports off: what they had summed goes, and the buffers unless a chain tracks
+static void free_signal(nvx_handle *h)
+{
+    if (!h->afc_tracking) free_signal_buffers(h);
+    for (auto &r : h->res) r.sig = false;                // (a launch still to be collected brings no records any more)
     for (auto &s : h->slots) s.sig = SigSums{};
-    h->sig_on = false; h->sig_stride = 0;
+    h->sig_on = false;
+}
+
+// nvx_afc_enable's buffers, made together at the first enable and released by free_handle
+static void free_afc(nvx_handle *h)
+{
+    for (int i = 0; i < 2; i++) { (void)hipFree(h->d_afc_k[i]); h->d_afc_k[i] = nullptr; }
+    (void)hipFree(h->d_afc_par); h->d_afc_par = nullptr;
+    for (auto &r : h->res) {
+        (void)hipFree(r.d_note); r.d_note = nullptr;
+        (void)hipHostFree(r.h_note); r.h_note = nullptr;
+        r.afc = false;
+    }
+    h->afc_tracking = 0;
 }
 
 // nvx_enable_soft's buffers and state, made together and released together: the soft character layers and the kept
@@ -149,6 +198,7 @@ static void free_handle(nvx_handle *h)
     (void)drain(h);
     snprintf(g_err, sizeof g_err, "%s", err.c_str());
     free_debug(h);
+    free_afc(h);
     free_signal(h);
     free_soft(h);
     for (auto it = h->made.rbegin(); it != h->made.rend(); ++it) {      // the streams, made first, go last
@@ -278,7 +328,7 @@ extern "C" int nvx_create(const nvx_config *cfg, nvx_handle **out)
         CR_MAKE(pinned, r.h_part, hipHostMalloc((void **)&r.h_part, (size_t)h->n_in * sizeof(nvx_part), hipHostMallocDefault));
         CR_MAKE(event, r.copied, hipEventCreateWithFlags(&r.copied, hipEventDisableTiming));
         CR_MAKE(event, r.done, hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
-        for (int i = 0; i < 8; i++) CR_MAKE(event, r.ev[i], hipEventCreate(&r.ev[i]));
+        for (int i = 0; i < 10; i++) CR_MAKE(event, r.ev[i], hipEventCreate(&r.ev[i]));
     }
     if (cfg->wideband)         // the channeliser's halo in front of a launch, two blocks by stream parity (nvx_kernels.h)
         for (int i = 0; i < 2; i++) CR_MAKE(device, h->d_whist[i], hipMalloc(&h->d_whist[i], (size_t)h->n_in * NVX_WB_HALO * 4));
@@ -307,6 +357,15 @@ extern "C" int nvx_create(const nvx_config *cfg, nvx_handle **out)
 }
 
 
+// a chain's tracking as the host sees it starts anew at the centre: counters, trace (the configuration stays)
+static void afc_restart(nvx_handle *h, int slot)
+{
+    AfcHost &a = h->slots[slot].afc;
+    a.k_last = h->tune_k[slot]; a.last_step = 0;
+    a.launches = a.updates = a.held = a.clamped = 0;
+    a.ring_w = a.ring_r = 0;
+}
+
 // Everything input streams [first, last) carry, set as a fresh handle has it (handle locked, nothing in flight).  An input
 // stream owns per_in decoded streams of two slots (chains) each; y2 rows go in slot order to the active slots only.
 static int clear_streams_locked(nvx_handle *h, int first, int last)
@@ -329,11 +388,16 @@ static int clear_streams_locked(nvx_handle *h, int first, int last)
         for (int i = 0; i < 2; i++)
             HIP_TRY(hipMemset2DAsync(h->d_y2[i] + row0 * h->y2_pitch, h->y2_pitch * sizeof(double2), 0, (size_t)NVX_Y2_PREFIX * sizeof(double2), n_rows, h->stream));
     }
+    // automatic frequency control: the tracked k returns to the centre (a reset is a new stream), tracking stays on
+    if (h->afc_tracking)
+        for (int i = 0; i < 2; i++)
+            HIP_TRY(hipMemcpyAsync(h->d_afc_k[i] + slot0, h->tune_k.data() + slot0, (size_t)n_sl * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     for (int k = slot0; k < slot0 + n_sl; k++) {
         Slot &s = h->slots[k];
         s.bits.clear(); s.base = 0; s.polled = 0;
         s.sig = SigSums{};
+        afc_restart(h, k);
         if (s.sitor) nvx_sitor_reset(s.sitor);
         if (s.soft_sitor) nvx_sitor_reset(s.soft_sitor);
         s.soft.clear(); s.soft_base = 0; s.soft_polled = 0; s.soft_count = 0;
@@ -464,7 +528,10 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     da.state_i = h->d_di; da.fsm_table = h->d_fsm_tab; da.words = h->d_words;
     da.bits = r.d_bits; da.bits_cap = h->bits_cap; da.nbits = r.d_nbits; da.dphi = h->d_dphi; da.ties = h->d_ties;
     da.corr = h->d_corr; da.csum = h->d_csum;
-    da.sig = h->sig_on ? r.d_sig : nullptr; da.sig_part = h->d_sig_part; da.sig_stride = h->sig_stride;
+    // automatic frequency control (navtex_amd_afc.h): while some chain tracks the launch carries the signal sums whether
+    // or not the user's reports are on, its cascade reads k from the array of its parity and nvx_afc_update follows the FSM
+    const bool afc = h->afc_tracking > 0;
+    da.sig = (h->sig_on || afc) ? r.d_sig : nullptr; da.sig_part = h->d_sig_part; da.sig_stride = h->sig_stride;
     da.soft = h->soft_mode ? r.d_soft : nullptr; da.soft_cap = std::min(h->soft_cap, n3_full / 8 + 8); da.soft_pos = h->d_soft_pos;
     nvx_forms forms = h->forms_req;                     // the request in, what the launchers took out
     forms.demod_tiles = nvx_front_tile_wgs(&da, forms.demod_tiles);
@@ -494,7 +561,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
         ca.queue = h->d_ctrl; ca.status = h->d_ctrl + 1; ca.done = h->d_ctrl + NVX_CASCADE_CTRL_INTS;
         ca.stage0_order = h->cfg.stage0_order;
         ca.third0 = third0;
-        ca.tune_k = h->d_tune_k;
+        ca.tune_k = afc ? h->d_afc_k[h->launched & 1] : h->d_tune_k;
         ca.max_waves_per_cu = -1;                        // one fewer than fit: room for the previous launch's demodulator (above)
         HIP_TRY(nvx_launch_cascade(&ca, h->cascade_raw, h->nch, &forms, st));
     }
@@ -517,7 +584,7 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     if (r.timed) HIP_TRY(hipEventRecord(r.ev[2], sd));
     HIP_TRY(nvx_launch_demod_front(&da, sd));
     if (r.timed) HIP_TRY(hipEventRecord(r.ev[3], sd));
-    if (!da.soft) HIP_TRY(hipEventRecord(h->demod_done[yb], sd));      // y3[yb] consumed
+    if (!da.soft && !afc) HIP_TRY(hipEventRecord(h->demod_done[yb], sd));      // y3[yb] consumed
     h->demod_pending[yb] = true;
     // FSM + bit download behind the front
     if (r.timed) HIP_TRY(hipEventRecord(r.ev[4], sd));
@@ -525,12 +592,23 @@ int nvx_launch_locked(nvx_handle *h, const void *d_iq, size_t pitch, size_t firs
     if (r.timed) HIP_TRY(hipEventRecord(r.ev[5], sd));
     // (soft values: the FSM kernel reads the bits' windows from y3[yb] too -- consumed only now; the cascade that waits for
     // this is the one after the next, which starts long after this FSM has run beside the next)
-    if (da.soft) HIP_TRY(hipEventRecord(h->demod_done[yb], sd));
+    // (tracking: the cascade that waits for this is also the next reader of the k array nvx_afc_update writes: K[L+2])
+    if (afc) {
+        nvx_afc_args aa{};
+        aa.sig = r.d_sig; aa.par = h->d_afc_par; aa.k_rw = h->d_afc_k[h->launched & 1]; aa.k_next = h->d_afc_k[(h->launched + 1) & 1];
+        aa.note = r.d_note; aa.n_slots = h->n_slots; aa.part = d_list; aa.n_part = r.n_part;
+        if (r.timed) HIP_TRY(hipEventRecord(r.ev[8], sd));
+        HIP_TRY(nvx_launch_afc_update(&aa, sd));
+        if (r.timed) HIP_TRY(hipEventRecord(r.ev[9], sd));
+    }
+    if (da.soft || afc) HIP_TRY(hipEventRecord(h->demod_done[yb], sd));
     HIP_TRY(hipMemcpyAsync(h->h_ties, h->d_ties, sizeof(nvx_tie_stats), hipMemcpyDeviceToHost, sd));
     HIP_TRY(hipMemcpyAsync(r.h_nbits, r.d_nbits, (size_t)h->n_slots * sizeof(int), hipMemcpyDeviceToHost, sd));
     HIP_TRY(hipMemcpyAsync(r.h_bits, r.d_bits, (size_t)h->n_slots * h->bits_cap, hipMemcpyDeviceToHost, sd));
-    if (da.sig) HIP_TRY(hipMemcpyAsync(r.h_sig, r.d_sig, (size_t)h->n_slots * sizeof(nvx_sig_rec), hipMemcpyDeviceToHost, sd));
-    r.sig = da.sig != nullptr;
+    if (h->sig_on) HIP_TRY(hipMemcpyAsync(r.h_sig, r.d_sig, (size_t)h->n_slots * sizeof(nvx_sig_rec), hipMemcpyDeviceToHost, sd));
+    r.sig = h->sig_on;
+    if (afc) HIP_TRY(hipMemcpyAsync(r.h_note, r.d_note, (size_t)h->n_slots * sizeof(nvx_afc_note), hipMemcpyDeviceToHost, sd));
+    r.afc = afc;
     // 4 bytes per bit: the rows are as long as this launch's bits can reach (a bit takes at least eight samples; bits_cap
     // above), so that one copy moves them all
     if (da.soft) HIP_TRY(hipMemcpyAsync(r.h_soft, r.d_soft, (size_t)h->n_slots * da.soft_cap * sizeof(float), hipMemcpyDeviceToHost, sd));
@@ -641,7 +719,9 @@ int nvx_collect_locked(nvx_handle *h, uint64_t upto)
                 h->ms[3] = fsm_ms;                        // ... and the FSM kernel alone
                 h->ms[2] = 0.f;
                 if (h->d_y2[0]) HIP_TRY(hipEventElapsedTime(&h->ms[2], r.ev[6], r.ev[7]));
-                h->ms_sum[0] += h->ms[0]; h->ms_sum[1] += h->ms[1]; h->ms_sum[2] += h->ms[2]; h->ms_sum[3] += h->ms[3]; h->ms_count++;
+                h->ms[4] = 0.f;
+                if (r.afc) HIP_TRY(hipEventElapsedTime(&h->ms[4], r.ev[8], r.ev[9]));
+                h->ms_sum[0] += h->ms[0]; h->ms_sum[1] += h->ms[1]; h->ms_sum[2] += h->ms[2]; h->ms_sum[3] += h->ms[3]; h->ms_sum[4] += h->ms[4]; h->ms_count++;
             }
             std::atomic<int> bad_slot{ -1 };
             // the chains of this launch: every slot, or (a launch with a participant list) the 2 * per_part slots of each
@@ -679,6 +759,14 @@ int nvx_collect_locked(nvx_handle *h, uint64_t upto)
                         g.samples += q.samples; g.b_samples += q.b_samples;
                         g.power += q.sum_power; g.dphi_b += q.sum_dphi_b; g.dphi2_b += q.sum_dphi2_b;
                         g.dphi_y += q.sum_dphi_y; g.dphi2_y += q.sum_dphi2_y; g.hi += q.sum_mf_hi; g.lo += q.sum_mf_lo;
+                    }
+                    if (r.afc && s.afc.on) {                                    // what nvx_afc_update noted of the launch
+                        const nvx_afc_note &q = r.h_note[i];
+                        AfcHost &a = s.afc;
+                        a.k_last = q.k; a.last_step = q.step; a.launches++;
+                        if (q.flags & NVX_AFC_F_UPDATE) a.updates++; else a.held++;
+                        if (q.flags & NVX_AFC_F_CLAMP) a.clamped++;
+                        a.ring[a.ring_w++ % NVX_AFC_TRACE_KEEP] = q.k;
                     }
                     if (s.bits.size() > 2 * h->bit_history) {                // a receiver runs for weeks: bound the poll history
                         const size_t drop = s.bits.size() - h->bit_history;
@@ -809,14 +897,14 @@ extern "C" size_t nvx_poll_bits(nvx_handle *h, int stream, int chain, char *out,
 }
 
 extern "C" void nvx_enable_timing(nvx_handle *h, int enabled) { if (h) h->timing = enabled != 0; }
-extern "C" float nvx_last_kernel_ms(nvx_handle *h, int which) { return (h && which >= 0 && which < 4) ? h->ms[which] : -1.f; }
+extern "C" float nvx_last_kernel_ms(nvx_handle *h, int which) { return (h && which >= 0 && which < 5) ? h->ms[which] : -1.f; }
 extern "C" int nvx_kernel_time_stats(nvx_handle *h, int which, double *sum_ms, uint64_t *launches, int reset)
 {
-    if (!h || which < 0 || which > 3) return NVX_ERR_ARG;
+    if (!h || which < 0 || which > 4) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     if (sum_ms) *sum_ms = h->ms_sum[which];
     if (launches) *launches = h->ms_count;
-    if (reset) { h->ms_sum[0] = h->ms_sum[1] = h->ms_sum[2] = h->ms_sum[3] = 0.0; h->ms_count = 0; }
+    if (reset) { h->ms_sum[0] = h->ms_sum[1] = h->ms_sum[2] = h->ms_sum[3] = h->ms_sum[4] = 0.0; h->ms_count = 0; }
     return NVX_OK;
 }
 
@@ -882,21 +970,7 @@ extern "C" int nvx_enable_signal_report(nvx_handle *h, int on)
     { int rc = drain(h); if (rc != NVX_OK) return rc; }
     if (!on) { free_signal(h); return NVX_OK; }
     if (h->sig_on) return NVX_OK;
-    // partials per slot: one, or (the tile-parallel front) the head's and one per tile from the third on
-    const int tiles = (h->y3_cap + NVX_FRONT_TILE - 1) / NVX_FRONT_TILE;
-    const int stride = std::max(1, tiles - 1);
-    const size_t rec = (size_t)h->n_slots * sizeof(nvx_sig_rec);
-    hipError_t e = hipMalloc(&h->d_sig_part, rec * (size_t)stride);
-    for (auto &r : h->res) {
-        if (e == hipSuccess) e = hipMalloc(&r.d_sig, rec);
-        if (e == hipSuccess) e = hipHostMalloc((void **)&r.h_sig, rec, hipHostMallocDefault);
-    }
-    if (e != hipSuccess) {
-        free_signal(h);
-        nvx_set_error("nvx_enable_signal_report: allocation failed: %s", hipGetErrorString(e));
-        return e == hipErrorOutOfMemory ? NVX_ERR_NOMEM : NVX_ERR_HIP;
-    }
-    h->sig_stride = stride;
+    { int rc = make_signal_buffers(h, "nvx_enable_signal_report"); if (rc != NVX_OK) return rc; }
     h->sig_on = true;
     return NVX_OK;
 }
@@ -973,6 +1047,15 @@ extern "C" uint64_t nvx_soft_count(nvx_handle *h, int stream, int chain)
     return h->slots[2 * stream + chain].soft_count;
 }
 
+// a slot's centre into both k arrays and its parameters (while some chain tracks; nothing of the handle's in flight)
+static int afc_write_centre(nvx_handle *h, int slot, int k)
+{
+    for (int i = 0; i < 2; i++) HIP_TRY(hipMemcpy(h->d_afc_k[i] + slot, &k, sizeof(int), hipMemcpyHostToDevice));
+    h->slots[slot].afc.par.kc = k;
+    HIP_TRY(hipMemcpy(h->d_afc_par + slot, &h->slots[slot].afc.par, sizeof(nvx_afc_par), hipMemcpyHostToDevice));
+    return NVX_OK;
+}
+
 // Carrier tuning (navtex_amd_tune.h).  The launches in flight keep the k they were launched with: the handle's work is
 // waited for, then the device array is rewritten, so the stream's next launch is the first with the new k.
 extern "C" int nvx_set_carrier(nvx_handle *h, int stream, int chain, double offset_hz, double *applied_hz)
@@ -985,11 +1068,15 @@ extern "C" int nvx_set_carrier(nvx_handle *h, int stream, int chain, double offs
     const int k = (int)std::rint(offset_hz / NVX_TUNE_STEP_HZ);
     std::lock_guard<std::mutex> lk(h->mu);
     HIP_TRY(hipSetDevice(h->cfg.device));
-    { int rc = drain(h); if (rc != NVX_OK) return rc; }
     const int slot = 2 * stream + chain;
+    // (a tracking chain restarts at its new centre: what its launches so far noted is taken in first)
+    if (h->slots[slot].afc.on) { int rc = nvx_collect_locked(h); if (rc != NVX_OK) return rc; }
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
     HIP_TRY(hipMemcpyAsync(h->d_tune_k + slot, &k, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (h->afc_tracking) { int rc = afc_write_centre(h, slot, k); if (rc != NVX_OK) return rc; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->tune_k[slot] = k;
+    afc_restart(h, slot);
     if (applied_hz) *applied_hz = k * NVX_TUNE_STEP_HZ;
     return NVX_OK;
 }
@@ -1004,6 +1091,154 @@ extern "C" int nvx_get_carrier(nvx_handle *h, int stream, int chain, double *off
     if (offset_hz) *offset_hz = k * NVX_TUNE_STEP_HZ;
     if (reference_mixer) *reference_mixer = k == (chain ? -NVX_TUNE_NOMINAL_K : NVX_TUNE_NOMINAL_K);
     return NVX_OK;
+}
+
+// ------------------------------------------------------------ automatic frequency control (navtex_amd_afc.h)
+extern "C" void nvx_afc_config_default(nvx_afc_config *c)
+{
+    if (!c) return;
+    memset(c, 0, sizeof *c);
+    c->struct_size = (uint32_t)sizeof *c;
+    c->gain_shift = 1; c->max_step = 8; c->range_k = 48; c->min_samples = 256; c->contrast_min = 0.7;
+}
+
+// the checks every AFC call shares; leaves the handle's slot in *slot
+static int afc_args(nvx_handle *h, int stream, int chain, const char *what, int *slot)
+{
+    if (!h) { nvx_set_error("%s: null handle", what); return NVX_ERR_ARG; }
+    if (h->cfg.wideband) { nvx_set_error("%s: not for wideband handles (the channeliser fixes their sub-bands)", what); return NVX_ERR_STATE; }
+    if (stream < 0 || stream >= h->n_streams || chain < 0 || chain > 1) { nvx_set_error("%s: bad stream or chain", what); return NVX_ERR_ARG; }
+    if (!((h->masks[stream] >> chain) & 1)) { nvx_set_error("%s: chain %d is not in stream %d's mask", what, chain, stream); return NVX_ERR_ARG; }
+    *slot = 2 * stream + chain;
+    return NVX_OK;
+}
+
+// the buffers of tracking, at the first enable: both k arrays at the chains' centres, nobody tracking
+static int make_afc(nvx_handle *h)
+{
+    if (h->d_afc_par) return NVX_OK;
+    const size_t n = (size_t)h->n_slots;
+    hipError_t e = hipMalloc(&h->d_afc_par, n * sizeof(nvx_afc_par));
+    if (e != hipSuccess) h->d_afc_par = nullptr;
+    for (int i = 0; i < 2; i++) if (e == hipSuccess) e = hipMalloc(&h->d_afc_k[i], n * sizeof(int));
+    for (auto &r : h->res) {
+        if (e == hipSuccess) e = hipMalloc(&r.d_note, n * sizeof(nvx_afc_note));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&r.h_note, n * sizeof(nvx_afc_note), hipHostMallocDefault);
+    }
+    if (e == hipSuccess) {
+        std::vector<nvx_afc_par> par(n);
+        for (size_t i = 0; i < n; i++) { par[i] = h->slots[i].afc.par; par[i].track = 0; par[i].kc = h->tune_k[i]; }
+        e = hipMemcpy(h->d_afc_par, par.data(), n * sizeof(nvx_afc_par), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        free_afc(h);
+        nvx_set_error("nvx_afc_enable: allocation failed: %s", hipGetErrorString(e));
+        return e == hipErrorOutOfMemory ? NVX_ERR_NOMEM : NVX_ERR_HIP;
+    }
+    return NVX_OK;
+}
+
+extern "C" int nvx_afc_enable(nvx_handle *h, int stream, int chain, const nvx_afc_config *cfg)
+{
+    int slot = 0;
+    { int rc = afc_args(h, stream, chain, "nvx_afc_enable", &slot); if (rc != NVX_OK) return rc; }
+    nvx_afc_config c;
+    nvx_afc_config_default(&c);
+    if (cfg) {
+        if (cfg->struct_size != sizeof(nvx_afc_config)) { nvx_set_error("nvx_afc_enable: nvx_afc_config.struct_size is %u, this library's has %zu bytes", cfg->struct_size, sizeof(nvx_afc_config)); return NVX_ERR_ARG; }
+        c = *cfg;
+    }
+    if (c.gain_shift < 0 || c.gain_shift > 4 || c.max_step < 1 || c.max_step > 64 || c.range_k < 1 || c.range_k > 320 || c.min_samples < 0 ||
+        !(c.contrast_min >= 0.0 && c.contrast_min <= 1.0)) {
+        nvx_set_error("nvx_afc_enable: a field out of range (gain_shift 0..4, max_step 1..64, range_k 1..320, min_samples >= 0, contrast_min 0..1)");
+        return NVX_ERR_ARG;
+    }
+    if (!nvx_launch_afc_update) { nvx_set_error("nvx_afc_enable: this build holds no update kernel"); return NVX_ERR_STATE; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->poisoned) return nvx_poisoned_error(h);
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    { int rc = nvx_collect_locked(h); if (rc != NVX_OK) return rc; }      // what is in flight is taken in: its launches did not track
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
+    { int rc = make_signal_buffers(h, "nvx_afc_enable"); if (rc != NVX_OK) return rc; }
+    { int rc = make_afc(h); if (rc != NVX_OK) { if (!h->sig_on && !h->afc_tracking) free_signal_buffers(h); return rc; } }
+    AfcHost &a = h->slots[slot].afc;
+    if (!h->afc_tracking)            // nobody tracked: the arrays may be stale (the launches read d_tune_k meanwhile)
+        for (int i = 0; i < 2; i++) HIP_TRY(hipMemcpy(h->d_afc_k[i], h->tune_k.data(), (size_t)h->n_slots * sizeof(int), hipMemcpyHostToDevice));
+    a.par.track = 1;
+    a.par.gain_shift = c.gain_shift; a.par.max_step = c.max_step; a.par.range_k = c.range_k; a.par.min_samples = c.min_samples;
+    a.par.contrast_min = c.contrast_min;
+    { int rc = afc_write_centre(h, slot, h->tune_k[slot]); if (rc != NVX_OK) { a.par.track = a.on ? 1 : 0; return rc; } }
+    if (a.ring.empty()) a.ring.assign(NVX_AFC_TRACE_KEEP, 0);
+    if (!a.on) { a.on = true; h->afc_tracking++; }
+    afc_restart(h, slot);
+    return NVX_OK;
+}
+
+extern "C" int nvx_afc_disable(nvx_handle *h, int stream, int chain, int keep)
+{
+    int slot = 0;
+    { int rc = afc_args(h, stream, chain, "nvx_afc_disable", &slot); if (rc != NVX_OK) return rc; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->poisoned) return nvx_poisoned_error(h);
+    AfcHost &a = h->slots[slot].afc;
+    if (!a.on) return NVX_OK;
+    HIP_TRY(hipSetDevice(h->cfg.device));
+    { int rc = nvx_collect_locked(h); if (rc != NVX_OK) return rc; }
+    { int rc = drain(h); if (rc != NVX_OK) return rc; }
+    int k = h->tune_k[slot];
+    if (keep) {                      // the tracked k: what the chain's next launch would have run with
+        HIP_TRY(hipMemcpy(&k, h->d_afc_k[h->launched & 1] + slot, sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h->d_tune_k + slot, &k, sizeof(int), hipMemcpyHostToDevice));
+        h->tune_k[slot] = k;
+    }
+    a.par.track = 0;
+    { int rc = afc_write_centre(h, slot, k); if (rc != NVX_OK) return rc; }
+    a.on = false; h->afc_tracking--;
+    afc_restart(h, slot);
+    if (!h->afc_tracking && !h->sig_on) free_signal_buffers(h);
+    return NVX_OK;
+}
+
+// what has finished is taken in, without waiting (nvx_poll)
+static int afc_take_in(nvx_handle *h)
+{
+    if (h->poisoned) return nvx_poisoned_error(h);
+    if (h->collected != h->launched) {
+        HIP_TRY(hipSetDevice(h->cfg.device));
+        return nvx_collect_ready_locked(h);
+    }
+    return NVX_OK;
+}
+
+extern "C" int nvx_afc_read(nvx_handle *h, int stream, int chain, nvx_afc_status *out)
+{
+    int slot = 0;
+    { int rc = afc_args(h, stream, chain, "nvx_afc_read", &slot); if (rc != NVX_OK) return rc; }
+    if (!out) { nvx_set_error("nvx_afc_read: null argument"); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    { int rc = afc_take_in(h); if (rc != NVX_OK) return rc; }
+    const AfcHost &a = h->slots[slot].afc;
+    memset(out, 0, sizeof *out);
+    out->enabled = a.on; out->centre_k = h->tune_k[slot];
+    out->k_last = a.on ? a.k_last : h->tune_k[slot]; out->last_step = a.on ? a.last_step : 0;
+    out->offset_hz = out->k_last * NVX_TUNE_STEP_HZ;
+    out->launches = a.launches; out->updates = a.updates; out->held = a.held; out->clamped = a.clamped;
+    return NVX_OK;
+}
+
+extern "C" int nvx_afc_trace(nvx_handle *h, int stream, int chain, int32_t *k, size_t cap)
+{
+    int slot = 0;
+    { int rc = afc_args(h, stream, chain, "nvx_afc_trace", &slot); if (rc != NVX_OK) return rc; }
+    if (!k && cap) { nvx_set_error("nvx_afc_trace: null argument"); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    { int rc = afc_take_in(h); if (rc != NVX_OK) return rc; }
+    AfcHost &a = h->slots[slot].afc;
+    if (!a.on) return 0;
+    if (a.ring_w - a.ring_r > NVX_AFC_TRACE_KEEP) a.ring_r = a.ring_w - NVX_AFC_TRACE_KEEP;     // the reader fell behind the ring
+    int n = 0;
+    while (a.ring_r < a.ring_w && (size_t)n < cap) k[n++] = a.ring[a.ring_r++ % NVX_AFC_TRACE_KEEP];
+    return n;
 }
 
 // the derived fields of navtex_amd_signal.h, in double; NaN where a denominator is 0

@@ -20,6 +20,7 @@
 #include "navtex_amd.h"
 #include "nvx_internal.h"
 #include "nvx_kernels.h"
+#include "nvx_afc_law.h"
 #include "nvx_pool.h"
 
 #define HIP_TRY(expr)                                                                      \
@@ -50,6 +51,15 @@ struct SigSums {                       // a chain's signal report (navtex_amd_si
     double power = 0.0, dphi_b = 0.0, dphi2_b = 0.0, dphi_y = 0.0, dphi2_y = 0.0, hi = 0.0, lo = 0.0;
 };
 
+struct AfcHost {                       // a chain's tracking as the host sees it (navtex_amd_afc.h): configuration, and what the
+    bool on = false;                   // collected launches' notes said since enable / reset / nvx_set_carrier
+    nvx_afc_par par{};
+    int k_last = 0, last_step = 0;
+    uint64_t launches = 0, updates = 0, held = 0, clamped = 0;
+    std::vector<int32_t> ring;         // the k of the last NVX_AFC_TRACE_KEEP launches (made when tracking goes on)
+    uint64_t ring_w = 0, ring_r = 0;   // launches noted, launches nvx_afc_trace has handed out
+};
+
 struct Slot {                          // one (stream, chain)
     bool active = false;
     int label = 0;
@@ -66,6 +76,7 @@ struct Slot {                          // one (stream, chain)
     std::vector<float> soft;
     size_t soft_base = 0, soft_polled = 0;
     uint64_t soft_count = 0;
+    AfcHost afc;                       // automatic frequency control (navtex_amd_afc.h)
 };
 
 struct Result {                        // one in-flight launch's bit output
@@ -79,7 +90,7 @@ struct Result {                        // one in-flight launch's bit output
     unsigned long long g0_all = 0;     // no list: the 900 S/s sample count every stream had when the launch went out
     hipEvent_t copied = nullptr;       // push mode: the launch's host-to-device copies have left the staging sets
     hipEvent_t done = nullptr;
-    hipEvent_t ev[8] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };   // begin/end of cascade, demod front, demod FSM, nvx_fir3
+    hipEvent_t ev[10] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };   // begin/end of cascade, demod front, demod FSM, nvx_fir3, nvx_afc_update
     bool timed = false;
     bool pending = false;
     // signal reports (nvx_enable_signal_report): the launch's record per slot, device and pinned; sig = the launch carried them
@@ -89,6 +100,10 @@ struct Result {                        // one in-flight launch's bit output
     float *d_soft = nullptr, *h_soft = nullptr;
     bool soft = false;
     int soft_pitch = 0;                // values per slot in this launch's rows (as long as its bits can reach, at most soft_cap)
+    // automatic frequency control (nvx_afc_enable): the update kernel's notes per slot, device and pinned (not on wideband
+    // handles); afc = the launch carried them
+    nvx_afc_note *d_note = nullptr, *h_note = nullptr;
+    bool afc = false;
 };
 
 // Decode latency of the live path (r4).  The reference decodes synchronously, sample by sample, and calls add_message
@@ -178,6 +193,12 @@ struct nvx_handle {
     // carrier tuning (navtex_amd_tune.h): k per slot, and its device copy behind the chain masks (NVX_TUNE_K_OFFSET)
     std::vector<int> tune_k;
     int *d_tune_k = nullptr;
+    // automatic frequency control (navtex_amd_afc.h; not on wideband handles): while afc_tracking chains track, the cascade
+    // of launch L reads its k from d_afc_k[L & 1] instead of d_tune_k and nvx_afc_update writes K[L+2] there; the slots'
+    // parameters.  Every write of a chain's centre goes to d_tune_k and, while some chain tracks, to both arrays.
+    int *d_afc_k[2] = { nullptr, nullptr };
+    nvx_afc_par *d_afc_par = nullptr;
+    int afc_tracking = 0;
     int *d_di = nullptr;
     uint32_t *d_fsm_tab = nullptr;     // bit-period transition table of the demodulator FSM (nvx_fsm.h)
     unsigned short *d_words = nullptr;
@@ -214,8 +235,8 @@ struct nvx_handle {
     bool forms_known = false;
     // timing
     bool timing = false;
-    float ms[4] = { 0.f, 0.f, 0.f, 0.f };   // last collected launch: cascade, demodulator (front + FSM), nvx_fir3, the FSM kernel alone
-    double ms_sum[4] = { 0.0, 0.0, 0.0, 0.0 };   // over all collected launches since the last stats reset
+    float ms[5] = { 0.f, 0.f, 0.f, 0.f, 0.f };   // last collected launch: cascade, demodulator (front + FSM), nvx_fir3, the FSM kernel alone, nvx_afc_update
+    double ms_sum[5] = { 0.0, 0.0, 0.0, 0.0, 0.0 };   // over all collected launches since the last stats reset
     uint64_t ms_count = 0;
     // host
     std::vector<uint8_t> masks;

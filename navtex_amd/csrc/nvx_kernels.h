@@ -195,6 +195,23 @@ typedef struct {
                                /* the samples its decisions fell on (rows 16-byte aligned, as words)                       */
 } nvx_demod_args;
 
+/* Automatic frequency control (navtex_amd_afc.h; the law: nvx_afc_law.h).  nvx_afc_update runs behind nvx_demod_fsm of
+ * launch L, one lane per slot: it reads the slot's record of that launch, K[L] (the array the launch's cascade read) and
+ * K[L+1] (the other array), writes K[L+2] over K[L] and leaves a note.  The cascade of launch L + 2, the next reader of
+ * that array, waits for the event recorded behind this kernel.                                                      */
+typedef struct nvx_afc_par nvx_afc_par;       /* nvx_afc_law.h: a slot's parameters, a launch's note for a slot (the kernels */
+typedef struct nvx_afc_note nvx_afc_note;     /* that only share this header do not see the law)                            */
+typedef struct {
+    const nvx_sig_rec *sig;    /* [n_slots] records of launch L (those of its participants are this launch's)        */
+    const nvx_afc_par *par;    /* [n_slots] parameters                                                                */
+    int *k_rw;                 /* [n_slots] K[L] in, K[L+2] out                                                       */
+    const int *k_next;         /* [n_slots] K[L+1]                                                                    */
+    nvx_afc_note *note;        /* [n_slots] this launch's notes                                                       */
+    int n_slots;
+    const nvx_part *part;      /* the launch's participants (ascending by stream), or NULL = every stream            */
+    int n_part;
+} nvx_afc_args;
+
 typedef struct {
     const nvx_synth_desc *desc;
     const nvx_period *pool;
@@ -255,6 +272,13 @@ hipError_t nvx_launch_demod_front(const nvx_demod_args *a, hipStream_t s);
 hipError_t nvx_launch_demod_fsm(const nvx_demod_args *a, hipStream_t s);
 hipError_t nvx_launch_synth(const nvx_synth_args *a, int n_streams, hipStream_t s);
 double nvx_atan2_host(double y, double x);
+/* nvx_afc.hip: the update kernel's launcher.  nvx_api.cpp names it as a weak symbol: a build of the host runtime without
+ * the kernels (tests/harness/handle_lifecycle.cpp) links, and can never enable tracking */
+hipError_t nvx_launch_afc_update(const nvx_afc_args *a, hipStream_t s);
+/* the law on the host (nvx_afc_law.h), exported for tests as nvx_atan2_host is */
+int nvx_afc_step_host(int gain_shift, int max_step, int range_k, int min_samples, double contrast_min, int kc, int k0, int k1,
+                      unsigned samples, unsigned b_samples, double sum_dphi_b, double sum_dphi_y, double sum_mf_hi, double sum_mf_lo,
+                      unsigned *flags);
 #ifdef __cplusplus
 }
 #endif
