@@ -124,9 +124,12 @@ static void check_case(int L, int M, int T, uint64_t consumed, size_t n_in, int 
 
 int main(void)
 {
-    // L, M, T of 12000, 8000, 11025, 11025 / 2, 12500, 96000, 64000, 88200, 2000, 4000, 6250, 44100, 48000, 3000, 95999 / 2
+    // L, M, T of 12000, 8000, 11025, 11025 / 2, 12500, 96000, 64000, 88200, 2000, 4000, 6250, 44100, 48000, 3000, 95999 / 2;
+    // then the rows of three 16-byte words -- 72000 (T = 20), 67200 (24: the row is full), 75600 and 73332 (18) --, the full
+    // two-word row of 84000 (16) and the four-word row behind six zeros of 64800 (26)
     const int PLANS[][3] = { { 21, 1, 30 }, { 63, 2, 30 }, { 160, 7, 30 }, { 320, 7, 30 }, { 504, 25, 30 }, { 21, 8, 12 }, { 63, 16, 28 }, { 20, 7, 14 },
-                             { 126, 1, 30 }, { 63, 1, 30 }, { 1008, 25, 30 }, { 40, 7, 30 }, { 21, 4, 30 }, { 84, 1, 30 }, { 1000, 381, 12 } };
+                             { 126, 1, 30 }, { 63, 1, 30 }, { 1008, 25, 30 }, { 40, 7, 30 }, { 21, 4, 30 }, { 84, 1, 30 }, { 1000, 381, 12 },
+                             { 7, 2, 20 }, { 15, 4, 24 }, { 10, 3, 18 }, { 1000, 291, 18 }, { 3, 1, 16 }, { 35, 9, 26 } };
     const size_t lengths[] = { 1, 2, 10, 28, 29, 30, 63, 64, 65, 255, 256, 257, 800, 1027, 3 * 256 + 37 };
     const uint64_t positions[] = { 0, 1, 7, 29, 30, 4097, ((uint64_t)1 << 32) - 1000, ((uint64_t)1 << 40) + 6, ((uint64_t)1 << 62) - 5000 };
     const int chunkings[] = { 0, 1, 2, 3, 683, 2048 };

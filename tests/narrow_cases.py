@@ -1,7 +1,10 @@
-"""The narrowband interpolator's cases, shared by tests/test_narrow.py (CPU) and tests/test_gpu_narrow.py: the rates whose
-design is held to the two bars, rows of tones and noise and full-scale random rows in every format and kind, rows at the
-rails matched to a phase's taps, and the end-to-end cases -- audio and low-rate IQ sources, the path each takes and where its
-chain is tuned.  Nothing is kept: a test that wants several rows at once holds them itself for as long as it runs."""
+"""The narrowband interpolator's cases, shared by tests/test_narrow.py (CPU), tests/test_gpu_narrow.py and
+tests/test_gpu_narrow_edges.py: the rates whose design is held to the two bars, rows of tones and noise and full-scale random
+rows in every format and kind, rows at the rails matched to a phase's taps, and the end-to-end cases -- audio and low-rate IQ
+sources, the path each takes and where its chain is tuned.  Nothing is kept: a test that wants several rows at once holds
+them itself for as long as it runs.  Behind them what the two GPU files share: the rates whose tap row is three 16-byte words
+(or an exact or a six-zero row) and which format and kind runs at each, and the resident call under sentinels (_run_resident,
+_same, _first_difference)."""
 from __future__ import annotations
 
 import numpy as np
@@ -14,8 +17,10 @@ import signals
 
 # (rate_num, rate_den) whose taps are held to the bars
 DESIGN_RATES = ((2000, 1), (4000, 1), (11025, 2), (6000, 1), (8000, 1), (11025, 1), (12000, 1), (16000, 1), (22050, 1), (24000, 1),
-                (32000, 1), (44100, 1), (48000, 1), (50000, 1), (64000, 1), (88200, 1), (96000, 1), (12500, 1), (7350, 1))
-T_OF_RATE = {(64000, 1): 28, (88200, 1): 14, (96000, 1): 12}       # 30 everywhere else
+                (32000, 1), (44100, 1), (48000, 1), (50000, 1), (64000, 1), (88200, 1), (96000, 1), (12500, 1), (7350, 1),
+                (72000, 1), (67200, 1), (75600, 1), (70000, 1), (73332, 1), (84000, 1), (64800, 1))
+T_OF_RATE = {(64000, 1): 28, (88200, 1): 14, (96000, 1): 12,       # 30 everywhere else
+             (72000, 1): 20, (67200, 1): 24, (75600, 1): 18, (70000, 1): 22, (73332, 1): 18, (84000, 1): 16, (64800, 1): 26}
 
 # End to end: amplitude 8000 over noise 1500, signals.stream_text(seed), 40 phasing characters.
 #   source: "real" (audio: the I column of the generator) or "iq";  rate: of the source;  station: its centre in the source;
@@ -97,3 +102,71 @@ def rails(taps: np.ndarray, fmt: int, kind: int, windows: int, gap: int = 1) -> 
         rows.append(np.full((gap, 2), zero, dtype=dt))
     out = np.concatenate(rows)
     return out if kind == nr.IQ else np.ascontiguousarray(out[:, 0])
+
+
+# ------------------------------------------------------------------------------------------- the three-word rows (GPU edges)
+# (L, M, T) of the rates whose tap row the existing cases never reach: T = 18 .. 24 is three 16-byte words (TQ = 3: T = 24 fills
+# the row, the others have Tp - T zero taps in front), T = 16 an exact two-word row, T = 26 a four-word row behind six zeros
+EDGE_PLANS = {(72000, 1): (7, 2, 20), (67200, 1): (15, 4, 24), (75600, 1): (10, 3, 18), (70000, 1): (18, 5, 22), (73332, 1): (1000, 291, 18),
+              (144000, 2): (7, 2, 20), (84000, 1): (3, 1, 16), (64800, 1): (35, 9, 26)}
+_ALL = tuple((fmt, kind) for fmt in (nr.S16, nr.U8, nr.S8, nr.F32) for kind in (nr.IQ, nr.REAL))
+# (format, kind) run at each rate: all eight at 72 000 and 67 200, and each of the eight once more at one of the other three
+# TQ = 3 rates (two of the issue's six places would leave two kernels at two rates), so that every (format, kind) has three
+# rates with a three-word row; 144 000 / 2 is the plan of 72 000 once more
+EDGE_RUNS = {(72000, 1): _ALL, (67200, 1): _ALL,
+             (75600, 1): ((nr.S16, nr.IQ), (nr.S8, nr.REAL), (nr.F32, nr.IQ)),
+             (70000, 1): ((nr.S16, nr.REAL), (nr.U8, nr.IQ), (nr.F32, nr.REAL)),
+             (73332, 1): ((nr.U8, nr.REAL), (nr.S8, nr.IQ)),
+             (144000, 2): ((nr.S16, nr.IQ),),
+             (84000, 1): ((nr.S16, nr.IQ), (nr.F32, nr.REAL)), (64800, 1): ((nr.S16, nr.IQ), (nr.F32, nr.REAL))}
+EDGE_STREAMS, EDGE_SAMPLES = 3, 3 * 256 + 37
+
+
+def edge_rows(rate, fmt: int, kind: int) -> list:
+    """The rows of the three-tiles-and-a-ragged-fourth case at `rate`: EDGE_STREAMS x EDGE_SAMPLES samples, a seed each."""
+    return [signal(fmt, kind, EDGE_SAMPLES, 100 * fmt + 10 * kind + s + rate[0]) for s in range(EDGE_STREAMS)]
+
+
+# ------------------------------------------------------------------------------------------------ the resident call (GPU)
+SENTINEL = 0x5a5a1234
+
+
+def _run_resident(nv, c, rows, cuts, pitch_extra=0, out_first=0):
+    """The rows (all of one length, in the plan's format and kind) through nvx_nb_resident in calls of `cuts` samples; every
+    call's input is uploaded to the start of the input rows as whole rows: behind a call's n_in samples the row is full scale up
+    to the pitch, so a read behind n_in changes the output.  Sentinels around every output row.  Returns int16 [streams, outputs, 2]."""
+    ns, n = len(rows), len(rows[0])
+    assert sum(cuts) == n and ns == c.n_streams
+    dt = rows[0].dtype
+    comps = 2 if c.kind == nr.IQ else 1
+    start = c.position(0)
+    n_out = nr.outputs_after(start[0] + n, c.L, c.M) - start[1]
+    pitch_out = out_first + n_out + pitch_extra
+    pitch_in = (max(max(cuts), 1) + 15) // 16 * 16 + 16 * pitch_extra
+    d_in = nv.DeviceBuffer(ns * pitch_in * comps * dt.itemsize)
+    d_out = nv.DeviceBuffer(ns * pitch_out * 4)
+    d_out.upload(np.full(ns * pitch_out, SENTINEL, dtype=np.uint32))
+    block = np.empty((ns, pitch_in * comps), dtype=dt)
+    pos = made = 0
+    for cut in cuts:
+        block[:, cut * comps:] = 1.0 if dt == np.float32 else np.iinfo(dt).max
+        for s in range(ns):
+            block[s, :cut * comps] = rows[s][pos:pos + cut].reshape(-1)
+        d_in.upload(block)
+        got = c.resident(d_in, pitch_in, cut, d_out, pitch_out, out_first + made)
+        assert got == nr.outputs_after(start[0] + pos + cut, c.L, c.M) - nr.outputs_after(start[0] + pos, c.L, c.M), (pos, cut)
+        pos += cut; made += got
+    assert made == n_out and c.position(ns - 1) == (start[0] + n, start[1] + n_out)
+    words = d_out.download(ns * pitch_out * 4, dtype=np.uint32).reshape(ns, pitch_out)
+    d_in.free(); d_out.free()
+    assert np.all(words[:, :out_first] == SENTINEL) and np.all(words[:, out_first + n_out:] == SENTINEL), "words outside the span were written"
+    return np.ascontiguousarray(words[:, out_first:out_first + n_out]).view(np.int16).reshape(ns, n_out, 2)
+
+
+def _first_difference(got, want):
+    return int(np.argmax(np.any(got != want, axis=1)))
+
+
+def _same(got, want, what):
+    for s in range(len(want)):
+        assert got[s].shape == want[s].shape and np.array_equal(got[s], want[s]), (what, s, _first_difference(got[s], want[s]))

@@ -1,8 +1,11 @@
-"""The real-input converter's cases, shared by tests/test_real.py (CPU) and tests/test_gpu_real.py: the real row of a
+"""The real-input converter's cases, shared by tests/test_real.py (CPU), tests/test_gpu_real.py and
+tests/test_gpu_real_edges.py: the real row of a
 direct-sampling receiver at 504 kS/s with two stations -- 518 strong at 140 kHz, 490 weak under noise at 112 kHz, which the
 converter puts at +-14 kHz of a 252 kS/s stream --, what a user without the converter would do with it (naive), the same two
 stations built directly as complex (the reference row), tones on FFT bins, the rails, and full-scale random rows.  Nothing
-is kept: a test that wants several rows at once holds them itself for as long as it runs."""
+is kept: a test that wants several rows at once holds them itself for as long as it runs.  Behind them what the two GPU files
+share: the call lengths of the vector-store case and where the kernel's lanes stand at their ends (end_of_call), and the
+resident call under sentinels (_run_resident, _same, _first_difference)."""
 from __future__ import annotations
 
 import numpy as np
@@ -111,3 +114,81 @@ def signal(fmt: int, n: int, seed: int) -> np.ndarray:
     if fmt == rf.S8:
         return np.clip(np.rint(a16 / 128.0), -128, 127).astype(np.int8)
     return (a16 / 32768.0).astype(np.float32)
+
+
+# ------------------------------------------------------------------------------------------- the vector stores (GPU edges)
+TILE, REGION = 4096, 1024                 # outputs of a tile, and of the region of it a wave loads
+# outputs of a call: the last pair in wave 2, inside a lane's group of either width and three words into a store group; and a
+# multiple of 4 that is none of 8: the bytes' group of 8 pairs is cut, the store group whole
+VEC_OUTPUTS = (2 * TILE + 2967, 2 * TILE + 1028)
+VEC_CUT = TILE + 1001                     # an odd number of pairs: the call behind it starts on a word that is not 16-byte aligned
+VEC_STREAMS = 3
+
+
+def end_of_call(n: int, spt: int):
+    """Where the kernel's loads meet the end of a call of n outputs, from the kernel's layout (a wave loads a region of 1024
+    pairs of the tile in steps of 64 lanes x spt pairs; spt = 4, or 8 for the 8-bit formats): (wave, step, lane) of the group
+    the last pair lies in, the pairs of that group inside the call, and the words of the last store group of 4 inside it."""
+    last = (n - 1) % TILE
+    wave, r = divmod(last, REGION)
+    step, r = divmod(r, 64 * spt)
+    lane, k = divmod(r, spt)
+    return (wave, step, lane), k + 1, (n - 1) % 4 + 1
+
+
+def vec_rows(fmt: int, n_out: int) -> list:
+    """The rows of the vector-store case: VEC_STREAMS x 2 n_out samples, a seed each.  The last pair of the row, and of a
+    first call of VEC_CUT pairs, stands at the format's lowest value: within its call the pair's odd sample reaches the
+    call's last output alone, through the tap of weight 1, and only half of full scale and more is sure to move it."""
+    rows = [signal(fmt, 2 * n_out, 300 + 10 * fmt + s) for s in range(VEC_STREAMS)]
+    low = np.float32(-1.0) if fmt == rf.F32 else np.iinfo(rf.DTYPES[fmt]).min
+    for row in rows:
+        row[2 * VEC_CUT - 2:2 * VEC_CUT] = low
+        row[-2:] = low
+    return rows
+
+
+# ------------------------------------------------------------------------------------------------ the resident call (GPU)
+SENTINEL = 0x5a5a1234
+
+
+def _run_resident(nv, c, rows, cuts, pitch_extra=0, out_first=0, aligned=None):
+    """The rows ([n] samples each, all of one length) through nvx_real_resident in calls of `cuts` samples (even); every call's
+    input is uploaded to the start of the input rows as whole rows: behind a call's n_in samples the row is full scale up to
+    the pitch, so a read behind n_in changes the output.  Sentinels around every output row.  `aligned`, one flag per call: the
+    call's first output word of every row is (or is not) 16-byte aligned, which is what chooses between the 16-byte and the
+    word-by-word stores.  Returns int16 [streams, n / 2, 2]."""
+    ns, n = len(rows), len(rows[0])
+    assert sum(cuts) == n and ns == c.n_streams and n % 2 == 0
+    dt = rows[0].dtype
+    pitch_out = out_first + n // 2 + pitch_extra
+    pitch_in = (max(max(cuts), 1) + 15) // 16 * 16 + 16 * pitch_extra
+    d_in = nv.DeviceBuffer(ns * pitch_in * dt.itemsize)
+    d_out = nv.DeviceBuffer(ns * pitch_out * 4)
+    d_out.upload(np.full(ns * pitch_out, SENTINEL, dtype=np.uint32))
+    block = np.empty((ns, pitch_in), dtype=dt)
+    start = c.position(0)
+    pos = 0
+    for call, cut in enumerate(cuts):
+        block[:, cut:] = 1.0 if dt == np.float32 else np.iinfo(dt).max
+        for s in range(ns):
+            block[s, :cut] = rows[s][pos:pos + cut]
+        d_in.upload(block)
+        if aligned is not None:
+            assert ((d_out.ptr + 4 * (out_first + pos // 2)) % 16 == 0 and pitch_out % 4 == 0) == aligned[call], (call, out_first, pos, pitch_out)
+        c.resident(d_in, pitch_in, cut, d_out, pitch_out, out_first + pos // 2)
+        pos += cut
+    assert c.position(ns - 1) == (start[0] + n, start[1] + n // 2)
+    words = d_out.download(ns * pitch_out * 4, dtype=np.uint32).reshape(ns, pitch_out)
+    d_in.free(); d_out.free()
+    assert np.all(words[:, :out_first] == SENTINEL) and np.all(words[:, out_first + n // 2:] == SENTINEL), "words outside the span were written"
+    return np.ascontiguousarray(words[:, out_first:out_first + n // 2]).view(np.int16).reshape(ns, n // 2, 2)
+
+
+def _first_difference(got, want):
+    return int(np.argmax(np.any(got != want, axis=1)))
+
+
+def _same(got, want, what):
+    for s in range(len(want)):
+        assert got[s].shape == want[s].shape and np.array_equal(got[s], want[s]), (what, s, _first_difference(got[s], want[s]))

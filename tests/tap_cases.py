@@ -1,7 +1,10 @@
-"""The channel tap's cases, shared by tests/test_tap.py (CPU) and tests/test_gpu_tap.py: the rates whose design is held to the
+"""The channel tap's cases, shared by tests/test_tap.py (CPU), tests/test_gpu_tap.py and tests/test_gpu_tap_edges.py: the
+rates whose design is held to the
 two bars, rows of tones and noise and full-scale random rows, rows at the rails matched to a phase's taps, and the end-to-end
 cases -- a 252 kS/s row with stations, the taps that take them out, the way back through the interpolator and where the chain
-is tuned.  Nothing is kept: a test that wants several rows at once holds them itself for as long as it runs."""
+is tuned.  Nothing is kept: a test that wants several rows at once holds them itself for as long as it runs.  Behind them what
+the two GPU files share: the resident call under sentinels (_run_resident, _same), the shifts and pitches set and read back
+(_set_shifts, _flat), and the cut plan of the edge cases (edge_cuts)."""
 from __future__ import annotations
 
 from fractions import Fraction
@@ -100,3 +103,113 @@ def rails(taps: np.ndarray, L: int, M: int, windows: int) -> np.ndarray:
         out[q - T + 1:q + 1, 0] = np.where(s > 0, 32767, -32768)
         out[q - T + 1:q + 1, 1] = np.where(s > 0, -32768, 32767)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the edge cases (GPU edges)
+# Shifts per input and tap, Hz: input 0 has k = 0 and k = 15, input 1 k = -325 and k = 1 (odd steps: every bit of the sample's
+# index counts); the audio kind's pitches: kp = 341 at 12 kS/s (odd) and 512
+EDGE_SHIFTS = ((0.0, 922.9), (-20000.0, 61.5))
+EDGE_PITCHES = (999.0, 1500.0)
+# (tile_out, form, T) of the plans the edge cases run at
+EDGE_PLANS = {(2000, tp.IQ): (128, 1, 3602), (2016, tp.IQ): (128, 2, 3574), (12000, tp.REAL): (256, 1, 3602), (12000, tp.IQ): (256, 1, 602),
+              (96000, tp.IQ): (256, 2, 32)}
+
+
+def edge_cuts(L: int, M: int, T: int, tile_out: int) -> list:
+    """Calls of 0, 1, T - 2, T - 1, T, 5000, 0, 1, 130, 0, 1 samples -- the five behind the 5000 are shorter than the history, and
+    their state row is written from the one read -- and a rest that takes the total to 3 T + 9000 at least and is itself
+    longer than a tile: the last call has two tiles and takes its first window from a carried state row."""
+    cuts = [0, 1, T - 2, T - 1, T, 5000, 0, 1, 130, 0, 1]
+    return cuts + [max(3 * T + 9000 - sum(cuts), (tile_out + 1) * M // L + 1)]
+
+
+def edge_rows(n: int, fo: int) -> list:
+    """The two inputs of the cut case at output rate fo."""
+    return [signal(n, 400 + s + fo) for s in range(2)]
+
+
+def low_run(taps: np.ndarray) -> int:
+    """The largest sum of hl = h & 255 over 256 consecutive taps of a phase (over all of them where T < 256), wherever the run
+    starts: 32768 times it is what a constant row at the negative rail puts into an int32 run of low halves."""
+    hl = taps.astype(np.int64) & 255
+    w = min(tp.RUN, hl.shape[1])
+    cs = np.concatenate([np.zeros((len(hl), 1), dtype=np.int64), np.cumsum(hl, axis=1)], axis=1)
+    return int((cs[:, w:] - cs[:, :-w]).max())
+
+
+# ------------------------------------------------------------------------------------------------ the resident call (GPU)
+SENTINEL = {tp.IQ: 0x5a5a1234, tp.REAL: 0x5a5a}
+OUT_DTYPE = {tp.IQ: np.uint32, tp.REAL: np.uint16}
+
+
+def _run_resident(nv, c, rows, cuts, pitch_extra=0, out_first=0):
+    """The inputs' rows (int16 [n, 2], all of one length) through nvx_tap_resident in calls of `cuts` samples; every call's
+    input is uploaded to the start of the input rows as whole rows: behind a call's n_in samples the row is full scale up to
+    the pitch, so a read behind n_in changes the output.  Sentinels around every output row.  Returns per output row int16
+    [outputs, 2] (IQ) or [outputs] (REAL)."""
+    ni, n = len(rows), len(rows[0])
+    assert sum(cuts) == n and ni == c.n_inputs
+    size, dt = tp_bytes(c.kind), OUT_DTYPE[c.kind]
+    start = c.position(0)
+    n_out = tp.outputs_after(start[0] + n, c.L, c.M) - start[1]
+    n_rows = ni * c.n_taps
+    pitch_out = out_first + n_out + pitch_extra
+    pitch_in = max(max(cuts), 1) + 3 + 5 * pitch_extra
+    d_in = nv.DeviceBuffer(ni * pitch_in * 4)
+    d_out = nv.DeviceBuffer(max(n_rows * pitch_out, 1) * size)
+    d_out.upload(np.full(max(n_rows * pitch_out, 1), SENTINEL[c.kind], dtype=dt))
+    block = np.empty((ni, pitch_in, 2), dtype=np.int16)
+    pos = made = 0
+    for cut in cuts:
+        block[:, cut:] = 32767
+        for s in range(ni):
+            block[s, :cut] = rows[s][pos:pos + cut]
+        d_in.upload(block)
+        got = c.resident(d_in, pitch_in, cut, d_out, pitch_out, out_first + made)
+        assert got == tp.outputs_after(start[0] + pos + cut, c.L, c.M) - tp.outputs_after(start[0] + pos, c.L, c.M), (pos, cut)
+        pos += cut; made += got
+    assert made == n_out and c.position(ni - 1) == (start[0] + n, start[1] + n_out)
+    words = d_out.download(max(n_rows * pitch_out, 1) * size, dtype=dt)[:n_rows * pitch_out].reshape(n_rows, pitch_out)
+    d_in.free(); d_out.free()
+    assert np.all(words[:, :out_first] == SENTINEL[c.kind]) and np.all(words[:, out_first + n_out:] == SENTINEL[c.kind]), "samples outside the span were written"
+    body = np.ascontiguousarray(words[:, out_first:out_first + n_out]).view(np.int16)
+    return [body[r].reshape(n_out, 2) if c.kind == tp.IQ else body[r] for r in range(n_rows)]
+
+
+def tp_bytes(kind):
+    return 4 if kind == tp.IQ else 2
+
+
+def _same(got, want, what):
+    assert len(got) == len(want)
+    for s in range(len(want)):
+        assert got[s].shape == want[s].shape, (what, s, got[s].shape, want[s].shape)
+        if not np.array_equal(got[s], want[s]):
+            diff = got[s] != want[s]
+            first = int(np.argmax(diff.reshape(len(diff), -1).any(axis=1)))
+            raise AssertionError((what, "row", s, "first difference at", first, got[s][first], want[s][first], "differences", int(diff.sum())))
+
+
+def _set_shifts(c, shifts, kind, pitches=None):
+    """Shifts (Hz per input and tap) and pitches (Hz per tap, every input) -> (ks per input, kps per tap) as applied."""
+    ks = []
+    for i, per_tap in enumerate(shifts):
+        for t, hz in enumerate(per_tap):
+            applied = c.set_shift(t, hz, input=i)
+            k = tp.grid(c.rate, kind, hz)
+            assert c.get_shift(t, i) == (k, applied) and applied == k * 252000 / 4096
+        ks.append([tp.grid(c.rate, kind, hz) for hz in per_tap])
+    kps = None
+    if kind == tp.REAL:
+        kps = []
+        for t, hz in enumerate(pitches):
+            if hz is not None:
+                applied = c.set_pitch(t, hz)
+                assert applied == tp.pitch_grid(c.rate, hz) * c.rate / 4096
+            kps.append(c.get_pitch(t)[0])
+            assert kps[-1] == tp.pitch_grid(c.rate, hz if hz is not None else tp.DEFAULT_PITCH_HZ)
+    return ks, kps
+
+
+def _flat(per_input):
+    return [row for rows in per_input for row in rows]

@@ -11,6 +11,7 @@ import pytest
 
 import narrow_cases as nc
 import narrow_ref as nr
+from narrow_cases import _first_difference, _run_resident, _same
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -18,7 +19,6 @@ FORMATS = (nr.S16, nr.U8, nr.S8, nr.F32)
 FORMAT_IDS = ("s16", "u8", "s8", "f32")
 KINDS = (nr.IQ, nr.REAL)
 KIND_IDS = ("iq", "real")
-SENTINEL = 0x5a5a1234
 # (rate_num, rate_den): M = 1; M = 2; L = 160, M = 7 (the window's parity alternates); L = 320 (two threads share a window);
 # L = 504, M = 25; T = 12
 RATES = ((12000, 1), (8000, 1), (11025, 1), (11025, 2), (12500, 1), (96000, 1))
@@ -47,47 +47,6 @@ def designs(nb):
             cache[(num, den)] = nb.design(num, den)
         return cache[(num, den)]
     return get
-
-
-def _run_resident(nv, c, rows, cuts, pitch_extra=0, out_first=0):
-    """The rows (all of one length, in the plan's format and kind) through nvx_nb_resident in calls of `cuts` samples; every
-    call's input is uploaded to the start of the input rows as whole rows: behind a call's n_in samples the row is full scale up
-    to the pitch, so a read behind n_in changes the output.  Sentinels around every output row.  Returns int16 [streams, outputs, 2]."""
-    ns, n = len(rows), len(rows[0])
-    assert sum(cuts) == n and ns == c.n_streams
-    dt = rows[0].dtype
-    comps = 2 if c.kind == nr.IQ else 1
-    start = c.position(0)
-    n_out = nr.outputs_after(start[0] + n, c.L, c.M) - start[1]
-    pitch_out = out_first + n_out + pitch_extra
-    pitch_in = (max(max(cuts), 1) + 15) // 16 * 16 + 16 * pitch_extra
-    d_in = nv.DeviceBuffer(ns * pitch_in * comps * dt.itemsize)
-    d_out = nv.DeviceBuffer(ns * pitch_out * 4)
-    d_out.upload(np.full(ns * pitch_out, SENTINEL, dtype=np.uint32))
-    block = np.empty((ns, pitch_in * comps), dtype=dt)
-    pos = made = 0
-    for cut in cuts:
-        block[:, cut * comps:] = 1.0 if dt == np.float32 else np.iinfo(dt).max
-        for s in range(ns):
-            block[s, :cut * comps] = rows[s][pos:pos + cut].reshape(-1)
-        d_in.upload(block)
-        got = c.resident(d_in, pitch_in, cut, d_out, pitch_out, out_first + made)
-        assert got == nr.outputs_after(start[0] + pos + cut, c.L, c.M) - nr.outputs_after(start[0] + pos, c.L, c.M), (pos, cut)
-        pos += cut; made += got
-    assert made == n_out and c.position(ns - 1) == (start[0] + n, start[1] + n_out)
-    words = d_out.download(ns * pitch_out * 4, dtype=np.uint32).reshape(ns, pitch_out)
-    d_in.free(); d_out.free()
-    assert np.all(words[:, :out_first] == SENTINEL) and np.all(words[:, out_first + n_out:] == SENTINEL), "words outside the span were written"
-    return np.ascontiguousarray(words[:, out_first:out_first + n_out]).view(np.int16).reshape(ns, n_out, 2)
-
-
-def _first_difference(got, want):
-    return int(np.argmax(np.any(got != want, axis=1)))
-
-
-def _same(got, want, what):
-    for s in range(len(want)):
-        assert got[s].shape == want[s].shape and np.array_equal(got[s], want[s]), (what, s, _first_difference(got[s], want[s]))
 
 
 # ------------------------------------------------------------------------------------------------------------------ (a)

@@ -10,12 +10,12 @@ import pytest
 
 import real_cases as rc
 import real_ref as rf
+from real_cases import _first_difference, _run_resident
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
 FORMATS = (rf.S16, rf.U8, rf.S8, rf.F32)
 FORMAT_IDS = ("s16", "u8", "s8", "f32")
-SENTINEL = 0x5a5a1234
 T = 4096                                  # outputs of a tile
 
 
@@ -31,39 +31,6 @@ def rl(nv):
     import navtex_amd.real
     assert navtex_amd.real.TILE == T
     return navtex_amd.real
-
-
-def _run_resident(nv, c, rows, cuts, pitch_extra=0, out_first=0):
-    """The rows ([n] samples each, all of one length) through nvx_real_resident in calls of `cuts` samples (even); every call's
-    input is uploaded to the start of the input rows as whole rows: behind a call's n_in samples the row is full scale up to
-    the pitch, so a read behind n_in changes the output.  Sentinels around every output row.  Returns int16 [streams, n / 2, 2]."""
-    ns, n = len(rows), len(rows[0])
-    assert sum(cuts) == n and ns == c.n_streams and n % 2 == 0
-    dt = rows[0].dtype
-    pitch_out = out_first + n // 2 + pitch_extra
-    pitch_in = (max(max(cuts), 1) + 15) // 16 * 16 + 16 * pitch_extra
-    d_in = nv.DeviceBuffer(ns * pitch_in * dt.itemsize)
-    d_out = nv.DeviceBuffer(ns * pitch_out * 4)
-    d_out.upload(np.full(ns * pitch_out, SENTINEL, dtype=np.uint32))
-    block = np.empty((ns, pitch_in), dtype=dt)
-    start = c.position(0)
-    pos = 0
-    for cut in cuts:
-        block[:, cut:] = 1.0 if dt == np.float32 else np.iinfo(dt).max
-        for s in range(ns):
-            block[s, :cut] = rows[s][pos:pos + cut]
-        d_in.upload(block)
-        c.resident(d_in, pitch_in, cut, d_out, pitch_out, out_first + pos // 2)
-        pos += cut
-    assert c.position(ns - 1) == (start[0] + n, start[1] + n // 2)
-    words = d_out.download(ns * pitch_out * 4, dtype=np.uint32).reshape(ns, pitch_out)
-    d_in.free(); d_out.free()
-    assert np.all(words[:, :out_first] == SENTINEL) and np.all(words[:, out_first + n // 2:] == SENTINEL), "words outside the span were written"
-    return np.ascontiguousarray(words[:, out_first:out_first + n // 2]).view(np.int16).reshape(ns, n // 2, 2)
-
-
-def _first_difference(got, want):
-    return int(np.argmax(np.any(got != want, axis=1)))
 
 
 # ------------------------------------------------------------------------------------------------------------------ (a)

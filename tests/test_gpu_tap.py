@@ -12,11 +12,10 @@ import pytest
 
 import tap_cases as tc
 import tap_ref as tr
+from tap_cases import _flat, _run_resident, _same, _set_shifts, tp_bytes
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
-SENTINEL = {tr.IQ: 0x5a5a1234, tr.REAL: 0x5a5a}
-OUT_DTYPE = {tr.IQ: np.uint32, tr.REAL: np.uint16}
 SHIFTS = ((0.0, 14000.0), (-14000.0, 5000.5), (60000.0, -100.0))       # per input and tap, Hz: one k = 0
 # (tile_out, form) the plan takes: form 1 = taps wave-uniform (L = 1 and waves * M a multiple of 4), 2 = per lane (L > 1, and
 # 2016 S/s: L = 1, M = 125, two waves)
@@ -45,79 +44,6 @@ def designs(tp):
             cache[(fo, kind)] = tp.design(fo, kind)
         return cache[(fo, kind)]
     return get
-
-
-def _run_resident(nv, c, rows, cuts, pitch_extra=0, out_first=0):
-    """The inputs' rows (int16 [n, 2], all of one length) through nvx_tap_resident in calls of `cuts` samples; every call's
-    input is uploaded to the start of the input rows as whole rows: behind a call's n_in samples the row is full scale up to
-    the pitch, so a read behind n_in changes the output.  Sentinels around every output row.  Returns per output row int16
-    [outputs, 2] (IQ) or [outputs] (REAL)."""
-    ni, n = len(rows), len(rows[0])
-    assert sum(cuts) == n and ni == c.n_inputs
-    size, dt = tp_bytes(c.kind), OUT_DTYPE[c.kind]
-    start = c.position(0)
-    n_out = tr.outputs_after(start[0] + n, c.L, c.M) - start[1]
-    n_rows = ni * c.n_taps
-    pitch_out = out_first + n_out + pitch_extra
-    pitch_in = max(max(cuts), 1) + 3 + 5 * pitch_extra
-    d_in = nv.DeviceBuffer(ni * pitch_in * 4)
-    d_out = nv.DeviceBuffer(max(n_rows * pitch_out, 1) * size)
-    d_out.upload(np.full(max(n_rows * pitch_out, 1), SENTINEL[c.kind], dtype=dt))
-    block = np.empty((ni, pitch_in, 2), dtype=np.int16)
-    pos = made = 0
-    for cut in cuts:
-        block[:, cut:] = 32767
-        for s in range(ni):
-            block[s, :cut] = rows[s][pos:pos + cut]
-        d_in.upload(block)
-        got = c.resident(d_in, pitch_in, cut, d_out, pitch_out, out_first + made)
-        assert got == tr.outputs_after(start[0] + pos + cut, c.L, c.M) - tr.outputs_after(start[0] + pos, c.L, c.M), (pos, cut)
-        pos += cut; made += got
-    assert made == n_out and c.position(ni - 1) == (start[0] + n, start[1] + n_out)
-    words = d_out.download(max(n_rows * pitch_out, 1) * size, dtype=dt)[:n_rows * pitch_out].reshape(n_rows, pitch_out)
-    d_in.free(); d_out.free()
-    assert np.all(words[:, :out_first] == SENTINEL[c.kind]) and np.all(words[:, out_first + n_out:] == SENTINEL[c.kind]), "samples outside the span were written"
-    body = np.ascontiguousarray(words[:, out_first:out_first + n_out]).view(np.int16)
-    return [body[r].reshape(n_out, 2) if c.kind == tr.IQ else body[r] for r in range(n_rows)]
-
-
-def tp_bytes(kind):
-    return 4 if kind == tr.IQ else 2
-
-
-def _same(got, want, what):
-    assert len(got) == len(want)
-    for s in range(len(want)):
-        assert got[s].shape == want[s].shape, (what, s, got[s].shape, want[s].shape)
-        if not np.array_equal(got[s], want[s]):
-            diff = got[s] != want[s]
-            first = int(np.argmax(diff.reshape(len(diff), -1).any(axis=1)))
-            raise AssertionError((what, "row", s, "first difference at", first, got[s][first], want[s][first], "differences", int(diff.sum())))
-
-
-def _set_shifts(c, shifts, kind, pitches=None):
-    """Shifts (Hz per input and tap) and pitches (Hz per tap, every input) -> (ks per input, kps per tap) as applied."""
-    ks = []
-    for i, per_tap in enumerate(shifts):
-        for t, hz in enumerate(per_tap):
-            applied = c.set_shift(t, hz, input=i)
-            k = tr.grid(c.rate, kind, hz)
-            assert c.get_shift(t, i) == (k, applied) and applied == k * 252000 / 4096
-        ks.append([tr.grid(c.rate, kind, hz) for hz in per_tap])
-    kps = None
-    if kind == tr.REAL:
-        kps = []
-        for t, hz in enumerate(pitches):
-            if hz is not None:
-                applied = c.set_pitch(t, hz)
-                assert applied == tr.pitch_grid(c.rate, hz) * c.rate / 4096
-            kps.append(c.get_pitch(t)[0])
-            assert kps[-1] == tr.pitch_grid(c.rate, hz if hz is not None else tr.DEFAULT_PITCH_HZ)
-    return ks, kps
-
-
-def _flat(per_input):
-    return [row for rows in per_input for row in rows]
 
 
 # ------------------------------------------------------------------------------------------------------------------ (a)

@@ -1,6 +1,6 @@
 """The narrowband interpolator (include/navtex_amd_narrow.h) on the CPU: the header and the companion library's exports and
 argument safety, L, M and every call's count against fractions.Fraction, the refusals, the taps handed out held to the
-project's two bars for nineteen rates, the launch arithmetic against 128-bit integers (a stand-alone program under ASan +
+project's two bars for twenty-six rates, the launch arithmetic against 128-bit integers (a stand-alone program under ASan +
 UBSan), the restatement (tests/narrow_ref.py) against Python integers and on cuts anywhere, and end to end through the
 restatement, the tuned chain's restatement and the oracle's character layer: six audio and low-rate IQ sources, each
 delivering exactly its text."""
@@ -107,7 +107,9 @@ def test_create_returns_nodev_without_a_gpu_and_refuses_bad_parameters_first(nv,
 # --------------------------------------------------------------------------------------------------------- rates, counts
 def test_l_m_and_the_refusals(nv, nb):
     want = {(12000, 1): (21, 1), (8000, 1): (63, 2), (11025, 1): (160, 7), (11025, 2): (320, 7), (12500, 1): (504, 25), (96000, 1): (21, 8),
-            (24000, 2): (21, 1), (2000, 1): (126, 1), (4000, 2): (126, 1), (192000, 2): (21, 8), (44100, 1): (40, 7), (7350, 1): (240, 7)}
+            (24000, 2): (21, 1), (2000, 1): (126, 1), (4000, 2): (126, 1), (192000, 2): (21, 8), (44100, 1): (40, 7), (7350, 1): (240, 7),
+            (72000, 1): (7, 2), (67200, 1): (15, 4), (75600, 1): (10, 3), (70000, 1): (18, 5), (73332, 1): (1000, 291), (144000, 2): (7, 2),
+            (84000, 1): (3, 1), (64800, 1): (35, 9)}
     for (num, den), (L, M) in want.items():
         f = Fraction(252000 * den, num)
         assert (f.numerator, f.denominator) == (L, M) == nr.ratio(num, den) == nb.design(num, den, taps=False)[:2], (num, den)
@@ -147,8 +149,10 @@ def designs(nb):
 @pytest.mark.parametrize("rate", nc.DESIGN_RATES, ids=lambda r: f"{r[0]}/{r[1]}")
 def test_the_taps_handed_out_hold_the_two_bars(designs, rate):
     """Every phase sums to exactly 2^14; sum |h| <= 65535; the pass band within +-0.1 dB from 0 to fp; at most -76 dB from
-    fi - fp to L fi / 2, on 8 points per side lobe.  Recorded from the C design: T = 30 (28 / 14 / 12 at 64 / 88.2 / 96 kS/s);
-    sum |h| at most 37 892 (28 288 at 96 kS/s); pass band within 0.0006 dB; stop band between -80.8 dB (L = 21) and -90.1 dB."""
+    fi - fp to L fi / 2, on 8 points per side lobe.  Recorded from the C design: T = 30 (28 / 14 / 12 at 64 / 88.2 / 96 kS/s, and
+    narrow_cases.T_OF_RATE's 16 .. 26 between 64.8 and 84 kS/s); sum |h| at most 37 892 (28 288 at 96 kS/s); pass band within
+    0.0010 dB (84 kS/s, L = 3; 0.0006 dB elsewhere); stop band between -77.3 dB (72 kS/s, L = 7, T = 20: 1.3 dB inside the bar;
+    -80.2 dB at 75.6 kS/s and -80.6 dB at 84 kS/s come next, then -80.8 dB at L = 21) and -90.1 dB."""
     num, den = rate
     L, M, T, h = designs[rate]
     fi = num / den
@@ -223,6 +227,29 @@ def test_the_rails_clamp_both_ways(designs):
         assert ref.acc_max >> 14 > 70000 and ref.acc_min >> 14 < -70000 and ref.acc_max <= big * 32768
         assert out.max() == 32767 and out.min() == -32768
         assert {int(out[:, 0].max()), int(out[:, 0].min()), int(out[:, 1].max()), int(out[:, 1].min())} == {32767, -32768}
+
+
+# ------------------------------------------------------------------------------------- the GPU edge cases, without a GPU
+def test_the_edge_cases_reach_every_kernel_of_three_word_rows_and_tell_a_tap_row_shifted_by_one_entry():
+    """What tests/test_gpu_narrow_edges.py reaches, from narrow_cases alone: for every format and kind at least three rates
+    with ceil(T / 8) = 3, a full row (T = 24) and a padded one (T = 20) among them; and T = 16, 24 and 26.  And its inputs
+    tell a wrong row from the right one: with every phase's taps moved by one entry, as a wrong number of zero taps in
+    front of the row would have them, every stream of every case differs from the restatement."""
+    runs = [(rate, fmt, kind) for rate, per_rate in nc.EDGE_RUNS.items() for fmt, kind in per_rate]
+    for fmt in (nr.S16, nr.U8, nr.S8, nr.F32):
+        for kind in (nr.IQ, nr.REAL):
+            ts = [nc.EDGE_PLANS[rate][2] for rate, f, k in runs if (f, k) == (fmt, kind) and rate[1] == 1]
+            three = [T for T in ts if (T + 7) // 8 == 3]
+            assert len(three) >= 3 and 24 in three and 20 in three, (fmt, kind, ts)
+    assert {16, 24, 26} <= {nc.EDGE_PLANS[rate][2] for rate, _, _ in runs}
+    for rate, fmt, kind in runs:
+        L, M, T, h = nr.design(*rate)
+        assert (L, M, T) == nc.EDGE_PLANS[rate]
+        moved = np.zeros_like(h)
+        moved[:, 1:] = h[:, :-1]
+        for row in nc.edge_rows(rate, fmt, kind):
+            want, wrong = nr.interpolate_all(row, h, L, M, fmt, kind)[0], nr.interpolate_all(row, moved, L, M, fmt, kind)[0]
+            assert (want != wrong).any(axis=1).mean() > 0.5, (rate, fmt, kind)
 
 
 # ------------------------------------------------------------------------------------------------------------ end to end

@@ -235,6 +235,28 @@ def test_a_tone_on_a_bin_has_unit_gain_and_its_image_is_below_76_dbc(b):
     assert naive_dbc > -10.0
 
 
+# ------------------------------------------------------------------------------------- the GPU edge cases, without a GPU
+@pytest.mark.parametrize("fmt", [rf.S16, rf.U8, rf.S8, rf.F32], ids=["s16", "u8", "s8", "f32"])
+def test_the_vector_store_case_ends_off_the_first_lanes_and_tells_a_zeroed_last_pair(fmt):
+    """tests/test_gpu_real_edges.py's lengths against the kernel's layout: the call's last pair in wave 2, inside a lane's
+    group of loads and of stores.  And its rows tell a wrong load from the right one: with the last pair of the group that
+    straddles the call's end read as zero, the call's last output differs in every stream -- for the one call, and for the
+    first of two calls cut at VEC_CUT pairs."""
+    spt = 8 if fmt in (rf.U8, rf.S8) else 4
+    (wave, step, lane), pairs, words = rc.end_of_call(rc.VEC_OUTPUTS[0], spt)
+    assert wave == 2 and (step, lane) != (0, 0) and 0 < pairs < spt and words == 3
+    assert rc.end_of_call(rc.VEC_OUTPUTS[1], spt)[1:] == (4, 4) and rc.VEC_CUT % 2 == 1 and rc.end_of_call(rc.VEC_CUT, spt)[1] < spt
+    for n_out in rc.VEC_OUTPUTS:
+        for row in rc.vec_rows(fmt, n_out):
+            want = rf.convert_all(row, fmt)[0]
+            c = rf.convert(row, fmt)
+            for n in (n_out, rc.VEC_CUT):
+                zeroed = c.copy()
+                zeroed[2 * n - 2:2 * n] = 0
+                right, wrong = rf.output_int(c, n - 1)[:2], rf.output_int(zeroed, n - 1)[:2]
+                assert right == tuple(int(v) for v in want[n - 1]) and wrong != right, (n_out, n)
+
+
 # ------------------------------------------------------------------------------------------------------------ end to end
 def test_the_acceptance_case(nv, oracle):
     """A real row at 504 kS/s: 518 at 140 kHz, amplitude 8000; 490 at 112 kHz, amplitude 300 under noise rc.NOISE; twelve seeds.

@@ -304,6 +304,41 @@ def test_the_rails_clamp_both_ways_and_the_sum_needs_more_than_32_bits(designs):
         assert {int(out[:, 0].max()), int(out[:, 0].min()), int(out[:, 1].max()), int(out[:, 1].min())} == {32767, -32768}
 
 
+# ------------------------------------------------------------------------------------- the GPU edge cases, without a GPU
+class _StateMovedByOneWord(tr.Tap):
+    """The restatement with one error: the carried row stands one word late."""
+
+    def push(self, x):
+        out = super().push(x)
+        self.hist = np.concatenate([np.zeros((1, 2), dtype=np.int64), self.hist[:-1]])
+        return out
+
+
+@pytest.mark.parametrize("plan", [(2000, tr.IQ), (2016, tr.IQ), (12000, tr.REAL)], ids=["iq_2000", "iq_2016", "real_12000"])
+def test_the_edge_cuts_tell_a_state_row_moved_by_one_word(tp, plan):
+    """tests/test_gpu_tap_edges.py's cut plan and inputs through the restatement and through one whose state row is moved by one
+    word behind every call: every call with outputs behind the first differs in every row -- the call of T samples, the one
+    of 5000, and the last, whose first windows lie in the carried row."""
+    fo, kind = plan
+    L, M, T, h = tp.design(fo, kind)
+    tile_out, _, t_want = tc.EDGE_PLANS[plan]
+    assert T == t_want
+    cuts = tc.edge_cuts(L, M, T, tile_out)
+    assert sum(cuts) >= 3 * T + 9000 and all(cut < T - 1 for cut in cuts[6:11]) and tr.outputs_after(cuts[-1], L, M) > tile_out
+    ks = [tr.grid(fo, kind, hz) for hz in tc.EDGE_SHIFTS[0]]
+    kps = [tr.pitch_grid(fo, hz) for hz in tc.EDGE_PITCHES] if kind == tr.REAL else None
+    assert ks[0] == 0 and ks[1] % 2 == 1 and (kps is None or kps[0] % 2 == 1)
+    x = tc.edge_rows(sum(cuts), fo)[0]
+    right, wrong = tr.Tap(h, L, M, kind, ks, kps), _StateMovedByOneWord(h, L, M, kind, ks, kps)
+    differing, pos = [], 0
+    for j, cut in enumerate(cuts):
+        a, b = right.push(x[pos:pos + cut]), wrong.push(x[pos:pos + cut])
+        pos += cut
+        if len(a[0]) and all(not np.array_equal(a[t], b[t]) for t in range(2)):
+            differing.append(j)
+    assert {4, 5, len(cuts) - 1} <= set(differing), differing
+
+
 # ------------------------------------------------------------------------------------------------------------ audio fold
 def test_a_tone_two_pitches_below_the_station_stays_76_db_below_it_in_the_audio(designs):
     """The REAL kind at 8 kS/s, pitch 1000 Hz: a full-scale tone at hz lands at 1000 Hz in the audio.  One at hz - 2000 Hz would,
