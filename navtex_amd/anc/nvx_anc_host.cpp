@@ -1,0 +1,396 @@
+// nvx_anc_host.cpp -- the noise canceller's entry points (include/navtex_amd_anc.h): the config checks, the plan with its
+// carried positions, state rows, block records and counters, the checks of a call, a push's staging, and the calls that
+// read or write a pair's state row (reset, set, set_mode, get).  The launch arithmetic is nvx_anc_plan.h's.  The library
+// stands alone: it shares no state with any other.
+#include <cstring>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "nvx_companion.h"
+#include "nvx_anc_plan.h"
+
+extern "C" const char *nvx_anc_last_error(void) { return nvx_error_text(); }
+
+static const uint32_t MAGIC = 0x4e414e31u;      // "NAN1"
+static const int BPS[4] = { 4, 2, 2, 8 };       // bytes per input sample, by format
+static const char *const NOUN = "the noise canceller";
+
+struct nvx_noise_canceller {
+    uint32_t magic = MAGIC;
+    std::mutex mu;
+    int device = 0, n_pairs = 0, format = 0, window_log2 = 0, state_words = 0;
+    int64_t *d_state[2] = { nullptr, nullptr };             // [n_pairs][state_words], read and written alternately
+    unsigned long long *d_counters = nullptr;               // [n_pairs][2]: blocks solved, blocks rejected
+    unsigned long long *d_records = nullptr;                // [pairs of a call][blocks of a call][NVX_ANC_SUMS]
+    size_t records_cap = 0;                                 // in records
+    std::vector<uint64_t> consumed, samples;                // samples: since creation
+    std::vector<uint8_t> parity;                            // which state row the pair's next launch reads
+    std::vector<uint8_t> mode;
+    nvx_event_timer timer;
+    void *d_push_in = nullptr; uint32_t *d_push_out = nullptr;      // a push's two input rows, one behind the other, and its output
+    size_t push_in_cap = 0, push_out_cap = 0;
+    struct { int chunks, tiles_per_chunk, records, form; } last = {};
+    int64_t kernel_launches = 0;
+
+    int64_t *row(int pair) { return d_state[parity[pair]] + (size_t)pair * state_words; }
+    int64_t *scalars(int pair) { return row(pair) + NVX_ANC_SUMS * ((size_t)1 << window_log2) + NVX_ANC_SUMS; }
+};
+
+static bool valid(const nvx_noise_canceller *c, const char *what)
+{
+    if (!c || c->magic != MAGIC) { set_error("%s: not a noise canceller", what); return false; }
+    return true;
+}
+
+static bool pair_ok(const nvx_noise_canceller *c, const char *what, int pair, int lowest)
+{
+    if (pair < lowest || pair >= c->n_pairs) { set_error("%s: pair %d of %d", what, pair, c->n_pairs); return false; }
+    return true;
+}
+
+extern "C" void nvx_anc_config_default(nvx_anc_config *cfg)
+{
+    if (!cfg) return;
+    memset(cfg, 0, sizeof *cfg);
+    cfg->struct_size = sizeof *cfg;
+    cfg->device = 0; cfg->format = NVX_ANC_CS16; cfg->n_pairs = 1; cfg->window_log2 = NVX_ANC_WINDOW_LOG2_DEFAULT;
+}
+
+// --------------------------------------------------------------------------------------------------------------- plans
+static void release(nvx_noise_canceller *c)
+{
+    (void)hipFree(c->d_state[0]); (void)hipFree(c->d_state[1]); (void)hipFree(c->d_counters); (void)hipFree(c->d_records);
+    (void)hipFree(c->d_push_in); (void)hipFree(c->d_push_out);
+    c->timer.destroy();
+    c->magic = 0;
+    delete c;
+}
+
+// Pairs [first, first + n) start anew: empty rows with the weight (0, 0) and each pair's mode, into the row its next launch
+// reads.  The caller holds the lock, has selected the device and has waited for it.
+static int write_fresh_rows(nvx_noise_canceller *c, int first, int n)
+{
+    const size_t sw = (size_t)c->state_words, scalars = sw - NVX_ANC_STATE_SCALARS;
+    std::vector<int64_t> image;
+    for (int i = first; i < first + n;) {
+        int j = i;
+        while (j < first + n && c->parity[j] == c->parity[i]) j++;
+        image.assign((size_t)(j - i) * sw, 0);
+        for (int k = i; k < j; k++) image[(size_t)(k - i) * sw + scalars + NVX_ANC_ST_MODE] = c->mode[k];
+        HIP_TRY(hipMemcpy(c->row(i), image.data(), image.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+        i = j;
+    }
+    return NVX_OK;
+}
+
+extern "C" int nvx_anc_create(const nvx_anc_config *cfg, nvx_noise_canceller **out)
+{
+    const char *what = "nvx_anc_create";
+    if (!cfg || !out) { set_error("%s: null argument", what); return NVX_ERR_ARG; }
+    *out = nullptr;
+    if (cfg->struct_size != sizeof *cfg) { set_error("%s: struct_size %u, this library's nvx_anc_config has %zu bytes", what, cfg->struct_size, sizeof *cfg); return NVX_ERR_ARG; }
+    if (cfg->n_pairs < 1 || cfg->n_pairs > 65535) { set_error("%s: n_pairs %d (1 .. 65535)", what, cfg->n_pairs); return NVX_ERR_ARG; }
+    if (cfg->format < NVX_ANC_CS16 || cfg->format > NVX_ANC_CF32) { set_error("%s: format %d (NVX_ANC_CS16 .. NVX_ANC_CF32)", what, cfg->format); return NVX_ERR_ARG; }
+    if (cfg->device < 0) { set_error("%s: device %d", what, cfg->device); return NVX_ERR_ARG; }
+    if (cfg->window_log2 != 2 && cfg->window_log2 != 4 && cfg->window_log2 != 6) { set_error("%s: window_log2 %d (2, 4 or 6)", what, cfg->window_log2); return NVX_ERR_ARG; }
+    nvx_noise_canceller *c = new (std::nothrow) nvx_noise_canceller;
+    if (!c) { set_error("%s: out of memory", what); return NVX_ERR_NOMEM; }
+    int rc = select_device(cfg->device, NOUN);
+    if (rc != NVX_OK) { release(c); return rc; }
+    c->device = cfg->device; c->n_pairs = cfg->n_pairs; c->format = cfg->format; c->window_log2 = cfg->window_log2;
+    c->state_words = NVX_ANC_STATE_WORDS(cfg->window_log2);
+    c->consumed.assign(cfg->n_pairs, 0); c->samples.assign(cfg->n_pairs, 0);
+    c->parity.assign(cfg->n_pairs, 0); c->mode.assign(cfg->n_pairs, NVX_ANC_TRACK);
+    const size_t state_bytes = (size_t)cfg->n_pairs * c->state_words * sizeof(int64_t), counter_bytes = (size_t)cfg->n_pairs * 2 * sizeof(unsigned long long);
+    hipError_t e = hipMalloc((void **)&c->d_state[0], state_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_state[1], state_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **)&c->d_counters, counter_bytes);
+    if (e != hipSuccess) { set_error("%s: allocation failed: %s", what, hipGetErrorString(e)); release(c); return NVX_ERR_NOMEM; }
+    e = hipMemset(c->d_state[1], 0, state_bytes);
+    if (e == hipSuccess) e = hipMemset(c->d_counters, 0, counter_bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { set_error("%s: clearing the state failed: %s", what, hipGetErrorString(e)); release(c); return NVX_ERR_HIP; }
+    if ((rc = write_fresh_rows(c, 0, cfg->n_pairs)) != NVX_OK) { release(c); return rc; }
+    *out = c;
+    return NVX_OK;
+}
+
+extern "C" void nvx_anc_destroy(nvx_noise_canceller *c)
+{
+    if (!c || c->magic != MAGIC) return;
+    (void)hipSetDevice(c->device);
+    (void)hipDeviceSynchronize();
+    release(c);
+}
+
+extern "C" int nvx_anc_plan(nvx_noise_canceller *c, int *format, int *n_pairs, int *window_log2)
+{
+    if (!valid(c, "nvx_anc_plan")) return NVX_ERR_ARG;
+    if (format) *format = c->format;
+    if (n_pairs) *n_pairs = c->n_pairs;
+    if (window_log2) *window_log2 = c->window_log2;
+    return NVX_OK;
+}
+
+// `pair` (-1: all) stands at `position` with nothing in front of it
+static int restart(nvx_noise_canceller *c, const char *what, int pair, uint64_t position)
+{
+    if (!pair_ok(c, what, pair, -1)) return NVX_ERR_ARG;
+    if (position >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc;
+    if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    const int first = pair < 0 ? 0 : pair, n = pair < 0 ? c->n_pairs : 1;
+    if ((rc = write_fresh_rows(c, first, n)) != NVX_OK) return rc;
+    for (int i = first; i < first + n; i++) c->consumed[i] = position;
+    return NVX_OK;
+}
+
+extern "C" int nvx_anc_reset(nvx_noise_canceller *c, int pair)
+{
+    return valid(c, "nvx_anc_reset") ? restart(c, "nvx_anc_reset", pair, 0) : NVX_ERR_ARG;
+}
+
+extern "C" int nvx_anc_debug_set_position(nvx_noise_canceller *c, int pair, uint64_t position)
+{
+    return valid(c, "nvx_anc_debug_set_position") ? restart(c, "nvx_anc_debug_set_position", pair, position) : NVX_ERR_ARG;
+}
+
+extern "C" int nvx_anc_position(nvx_noise_canceller *c, int pair, uint64_t *consumed)
+{
+    const char *what = "nvx_anc_position";
+    if (!valid(c, what) || !pair_ok(c, what, pair, 0)) return NVX_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (consumed) *consumed = c->consumed[pair];
+    return NVX_OK;
+}
+
+// `count` scalars of the state rows of `pair` (-1: all), from scalar `at` on, become `values`
+static int write_scalars(nvx_noise_canceller *c, int pair, int at, const int64_t *values, int count)
+{
+    int rc;
+    if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    for (int i = pair < 0 ? 0 : pair; i < (pair < 0 ? c->n_pairs : pair + 1); i++)
+        HIP_TRY(hipMemcpy(c->scalars(i) + at, values, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice));
+    return NVX_OK;
+}
+
+extern "C" int nvx_anc_set(nvx_noise_canceller *c, int pair, int c_re, int c_im)
+{
+    const char *what = "nvx_anc_set";
+    if (!valid(c, what) || !pair_ok(c, what, pair, -1)) return NVX_ERR_ARG;
+    if (c_re < -NVX_ANC_C_MAX || c_re > NVX_ANC_C_MAX || c_im < -NVX_ANC_C_MAX || c_im > NVX_ANC_C_MAX) {
+        set_error("%s: (%d, %d): |c_re|, |c_im| <= %d", what, c_re, c_im, NVX_ANC_C_MAX);
+        return NVX_ERR_ARG;
+    }
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int64_t v[2] = { c_re, c_im };
+    return write_scalars(c, pair, NVX_ANC_ST_CRE, v, 2);
+}
+
+extern "C" int nvx_anc_set_mode(nvx_noise_canceller *c, int pair, int mode)
+{
+    const char *what = "nvx_anc_set_mode";
+    if (!valid(c, what) || !pair_ok(c, what, pair, -1)) return NVX_ERR_ARG;
+    if (mode != NVX_ANC_TRACK && mode != NVX_ANC_HOLD) { set_error("%s: mode %d (NVX_ANC_TRACK or NVX_ANC_HOLD)", what, mode); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int64_t v = mode;
+    const int rc = write_scalars(c, pair, NVX_ANC_ST_MODE, &v, 1);
+    if (rc == NVX_OK)
+        for (int i = pair < 0 ? 0 : pair; i < (pair < 0 ? c->n_pairs : pair + 1); i++) c->mode[i] = (uint8_t)mode;
+    return rc;
+}
+
+extern "C" int nvx_anc_get(nvx_noise_canceller *c, int pair, nvx_anc_status *out)
+{
+    const char *what = "nvx_anc_get";
+    if (!valid(c, what) || !pair_ok(c, what, pair, 0)) return NVX_ERR_ARG;
+    if (!out) { set_error("%s: null argument", what); return NVX_ERR_ARG; }
+    std::lock_guard<std::mutex> lk(c->mu);
+    int rc;
+    if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
+    std::vector<int64_t> row((size_t)c->state_words);
+    unsigned long long counters[2] = { 0, 0 };
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(row.data(), c->row(pair), row.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(counters, c->d_counters + 2 * (size_t)pair, sizeof counters, hipMemcpyDeviceToHost));
+    const int W = 1 << c->window_log2;
+    const int64_t *sc = row.data() + NVX_ANC_SUMS * W + NVX_ANC_SUMS;
+    memset(out, 0, sizeof *out);
+    out->c_re = (int32_t)sc[NVX_ANC_ST_CRE]; out->c_im = (int32_t)sc[NVX_ANC_ST_CIM];
+    out->mode = (int32_t)sc[NVX_ANC_ST_MODE]; out->last_reason = (int32_t)sc[NVX_ANC_ST_REASON];
+    out->coherence_q14 = (int32_t)sc[NVX_ANC_ST_COHERENCE];
+    for (int b = 0; b < W; b++)                             // blocks not complete since the reset are zero
+        for (int k = 0; k < NVX_ANC_SUMS; k++) out->sums[k] += row[(size_t)b * NVX_ANC_SUMS + k];
+    out->samples = c->samples[pair]; out->blocks_solved = counters[0]; out->blocks_rejected = counters[1];
+    return NVX_OK;
+}
+
+extern "C" int nvx_anc_timing(nvx_noise_canceller *c, int enable)
+{
+    if (!valid(c, "nvx_anc_timing")) return NVX_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    c->timer.enabled = enable != 0;
+    return NVX_OK;
+}
+
+extern "C" int nvx_anc_time_stats(nvx_noise_canceller *c, double *sum_ms, uint64_t *calls, int reset)
+{
+    if (!valid(c, "nvx_anc_time_stats")) return NVX_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return c->timer.collect(sum_ms, calls, reset);
+}
+
+extern "C" int64_t nvx_anc_debug_last_launch(nvx_noise_canceller *c, int *chunks, int *tiles_per_chunk, int *records, int *form)
+{
+    if (!valid(c, "nvx_anc_debug_last_launch")) return NVX_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (c->kernel_launches) {
+        if (chunks) *chunks = c->last.chunks;
+        if (tiles_per_chunk) *tiles_per_chunk = c->last.tiles_per_chunk;
+        if (records) *records = c->last.records;
+        if (form) *form = c->last.form;
+    }
+    return c->kernel_launches;
+}
+
+// ------------------------------------------------------------------------------------------------------------ launches
+// One call over pairs [first, first + n) of the plan, which stand at `consumed` and read state row `parity`; the caller
+// holds the plan's lock and has checked every span.
+static int launch(nvx_noise_canceller *c, int first, int n, uint64_t consumed, int parity, const void *d_main, size_t pitch_main, const void *d_sense,
+                  size_t pitch_sense, size_t n_in, uint32_t *d_out, size_t pitch_out, size_t out_first, hipStream_t s)
+{
+    // a workgroup per pair fills the chip from a few workgroups per CU on; below that a pair's tiles are spread out
+    const int wanted = n >= 1024 ? 1 : (NVX_ANC_TARGET_WORKGROUPS + n - 1) / n;
+    nvx_anc_args a;
+    int chunks = nvx_anc_fill_args(consumed, d_main, pitch_main, d_sense, pitch_sense, n_in, d_out, pitch_out, out_first, n, nullptr, nullptr, nullptr,
+                                   nullptr, c->window_log2, wanted, &a);
+    // the call's block records, from zero
+    const size_t records = (size_t)n * (size_t)a.blocks;
+    if (records > c->records_cap) {
+        HIP_TRY(hipDeviceSynchronize());                    // an earlier call may still use the old ones
+        (void)hipFree(c->d_records); c->d_records = nullptr; c->records_cap = 0;
+        if (hipMalloc((void **)&c->d_records, records * NVX_ANC_SUMS * sizeof(unsigned long long)) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("%s: hipMalloc of %zu block records failed", "nvx_anc", records);
+            return NVX_ERR_NOMEM;
+        }
+        c->records_cap = records;
+    }
+    chunks = nvx_anc_fill_args(consumed, d_main, pitch_main, d_sense, pitch_sense, n_in, d_out, pitch_out, out_first, n,
+                               c->d_state[parity] + (size_t)first * c->state_words, c->d_state[parity ^ 1] + (size_t)first * c->state_words, c->d_records,
+                               c->d_counters + 2 * (size_t)first, c->window_log2, wanted, &a);
+    nvx_event_timer::events ev;
+    int rc;
+    if ((rc = c->timer.begin(s, ev)) != NVX_OK) return rc;
+    HIP_TRY(hipMemsetAsync(c->d_records, 0, records * NVX_ANC_SUMS * sizeof(unsigned long long), s));
+    HIP_TRY(nvx_anc_launch(&a, c->format, n, chunks, s));
+    c->last = { chunks, a.tiles_per_chunk, a.blocks, chunks > 1 ? 2 : 1 };
+    c->kernel_launches += 2;
+    if ((rc = c->timer.end(s, ev)) != NVX_OK) return rc;
+    for (int i = first; i < first + n; i++) { c->consumed[i] = consumed + n_in; c->samples[i] += n_in; c->parity[i] = (uint8_t)(parity ^ 1); }
+    return NVX_OK;
+}
+
+// [p, p + bytes) and [q, q + size) have a byte in common
+static bool overlap(const void *p, size_t bytes, const void *q, size_t size)
+{
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return bytes && size && a < b + size && b < a + bytes;
+}
+
+extern "C" int nvx_anc_resident(nvx_noise_canceller *c, const void *d_main, size_t pitch_main, const void *d_sense, size_t pitch_sense, size_t n_in,
+                                void *d_out, size_t pitch_out, size_t out_first, void *hip_stream)
+{
+    const char *what = "nvx_anc_resident";
+    if (!valid(c, what)) return NVX_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!d_main || !d_sense || !d_out || ((uintptr_t)d_main & 15) || ((uintptr_t)d_sense & 15) || ((uintptr_t)d_out & 3) || n_in > NVX_ANC_MAX_IN) {
+        set_error("%s: bad argument (null pointer, an input not 16-byte aligned, output not 4-byte aligned, or more than 2^30 samples)", what);
+        return NVX_ERR_ARG;
+    }
+    for (int i = 1; i < c->n_pairs; i++)
+        if (c->consumed[i] != c->consumed[0]) {
+            set_error("%s: pair %d stands at %llu, pair 0 at %llu: all pairs of a call stand at the same position", what, i,
+                      (unsigned long long)c->consumed[i], (unsigned long long)c->consumed[0]);
+            return NVX_ERR_STATE;
+        }
+    const uint64_t consumed = c->consumed[0];
+    if ((consumed + n_in) >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
+    // every row's last sample read and last word written, in samples of its row (out_end) and in bytes of the whole operand
+    const size_t rows = (size_t)c->n_pairs, bps = (size_t)BPS[c->format];
+    size_t out_end, main_bytes, sense_bytes, out_bytes;
+    if (__builtin_add_overflow(out_first, n_in, &out_end) || !span_bytes(rows - 1, pitch_main, n_in, bps, &main_bytes) ||
+        !span_bytes(rows - 1, pitch_sense, n_in, bps, &sense_bytes) || !span_bytes(rows - 1, pitch_out, out_end, 4, &out_bytes) ||
+        (uintptr_t)d_main + main_bytes < main_bytes || (uintptr_t)d_sense + sense_bytes < sense_bytes || (uintptr_t)d_out + out_bytes < out_bytes) {
+        set_error("%s: the span of %zu samples of %d pairs at pitch %zu or %zu, or of as many words from %zu at pitch %zu, overflows", what, n_in,
+                  c->n_pairs, pitch_main, pitch_sense, out_first, pitch_out);
+        return NVX_ERR_ARG;
+    }
+    if (rows > 1 && (n_in > pitch_main || ((pitch_main * bps) & 15) || n_in > pitch_sense || ((pitch_sense * bps) & 15) || out_end > pitch_out)) {
+        set_error("%s: %zu samples per pair at pitches %zu and %zu, words up to %zu at pitch %zu (a row must hold them, and input rows are 16-byte aligned)",
+                  what, n_in, pitch_main, pitch_sense, out_end, pitch_out);
+        return NVX_ERR_ARG;
+    }
+    // the words written, from the first to the last, against both inputs
+    const char *const out_lo = (const char *)d_out + out_first * 4;
+    const size_t out_span = out_bytes - out_first * 4;
+    if (overlap(out_lo, out_span, d_main, main_bytes) || overlap(out_lo, out_span, d_sense, sense_bytes)) {
+        set_error("%s: the output span (%zu bytes from %p) overlaps an input span (%zu bytes from %p, %zu bytes from %p): the second pass would read words "
+                  "the first has not seen", what, out_span, (const void *)out_lo, main_bytes, d_main, sense_bytes, d_sense);
+        return NVX_ERR_ARG;
+    }
+    if (n_in == 0) return NVX_OK;
+    int rc;
+    if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
+    if ((rc = check_device_span(d_main, main_bytes, what, "main input")) != NVX_OK) return rc;
+    if ((rc = check_device_span(d_sense, sense_bytes, what, "sense input")) != NVX_OK) return rc;
+    if ((rc = check_device_span(d_out, out_bytes, what, "output")) != NVX_OK) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    // the state rows of pairs pushed one by one are brought to pair 0's parity
+    const int parity = c->parity[0];
+    for (int i = 1; i < c->n_pairs; i++)
+        if (c->parity[i] != parity) {
+            HIP_TRY(hipMemcpyAsync(c->d_state[parity] + (size_t)i * c->state_words, c->d_state[parity ^ 1] + (size_t)i * c->state_words,
+                                   (size_t)c->state_words * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+            c->parity[i] = (uint8_t)parity;
+        }
+    return launch(c, 0, c->n_pairs, consumed, parity, d_main, pitch_main, d_sense, pitch_sense, n_in, (uint32_t *)d_out, pitch_out, out_first, s);
+}
+
+extern "C" int nvx_anc_push(nvx_noise_canceller *c, int pair, const void *main_in, const void *sense_in, size_t n_in, int16_t *out_iq)
+{
+    const char *what = "nvx_anc_push";
+    if (!valid(c, what)) return NVX_ERR_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (pair < 0 || pair >= c->n_pairs || !main_in || !sense_in || !out_iq || n_in > NVX_ANC_MAX_IN) {
+        set_error("%s: bad argument (pair %d of %d, null pointer, or more than 2^30 samples)", what, pair, c->n_pairs);
+        return NVX_ERR_ARG;
+    }
+    const uint64_t consumed = c->consumed[pair];
+    if ((consumed + n_in) >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
+    if (n_in == 0) return NVX_OK;
+    int rc;
+    if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
+    // the sense row lies behind the main row, 16-byte aligned
+    const size_t in_bytes = n_in * (size_t)BPS[c->format], row_bytes = (in_bytes + 15) & ~(size_t)15;
+    if (2 * row_bytes > c->push_in_cap) {
+        (void)hipFree(c->d_push_in); c->d_push_in = nullptr; c->push_in_cap = 0;
+        if (hipMalloc(&c->d_push_in, 2 * row_bytes) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, 2 * row_bytes); return NVX_ERR_NOMEM; }
+        c->push_in_cap = 2 * row_bytes;
+    }
+    if (n_in > c->push_out_cap) {
+        (void)hipFree(c->d_push_out); c->d_push_out = nullptr; c->push_out_cap = 0;
+        if (hipMalloc((void **)&c->d_push_out, n_in * 4) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, n_in * 4); return NVX_ERR_NOMEM; }
+        c->push_out_cap = n_in;
+    }
+    void *const d_sense = (char *)c->d_push_in + row_bytes;
+    HIP_TRY(hipMemcpy(c->d_push_in, main_in, in_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_sense, sense_in, in_bytes, hipMemcpyHostToDevice));
+    if ((rc = launch(c, pair, 1, consumed, c->parity[pair], c->d_push_in, n_in, d_sense, n_in, n_in, c->d_push_out, n_in, 0, nullptr)) != NVX_OK) return rc;
+    HIP_TRY(hipMemcpy(out_iq, c->d_push_out, n_in * 4, hipMemcpyDeviceToHost));     // waits for the null stream
+    return NVX_OK;
+}
