@@ -19,33 +19,24 @@ static const char *const NOUN = "the noise canceller";
 struct nvx_noise_canceller {
     uint32_t magic = MAGIC;
     std::mutex mu;
-    int device = 0, n_pairs = 0, format = 0, window_log2 = 0, state_words = 0;
-    int64_t *d_state[2] = { nullptr, nullptr };             // [n_pairs][state_words], read and written alternately
+    int device = 0, n_pairs = 0, format = 0, window_log2 = 0;
+    nvx_state_rows<int64_t> state;                          // [n_pairs][NVX_ANC_STATE_WORDS(window_log2)]
     unsigned long long *d_counters = nullptr;               // [n_pairs][2]: blocks solved, blocks rejected
     unsigned long long *d_records = nullptr;                // [pairs of a call][blocks of a call][NVX_ANC_SUMS]
     size_t records_cap = 0;                                 // in records
     std::vector<uint64_t> consumed, samples;                // samples: since creation
-    std::vector<uint8_t> parity;                            // which state row the pair's next launch reads
     std::vector<uint8_t> mode;
     nvx_event_timer timer;
-    void *d_push_in = nullptr; uint32_t *d_push_out = nullptr;      // a push's two input rows, one behind the other, and its output
-    size_t push_in_cap = 0, push_out_cap = 0;
+    nvx_push_staging push;                                  // a push's two input rows, one behind the other, and its output
     struct { int chunks, tiles_per_chunk, records, form; } last = {};
     int64_t kernel_launches = 0;
 
-    int64_t *row(int pair) { return d_state[parity[pair]] + (size_t)pair * state_words; }
-    int64_t *scalars(int pair) { return row(pair) + NVX_ANC_SUMS * ((size_t)1 << window_log2) + NVX_ANC_SUMS; }
+    int64_t *scalars(int pair) { return state.row(pair) + NVX_ANC_SUMS * ((size_t)1 << window_log2) + NVX_ANC_SUMS; }
 };
 
 static bool valid(const nvx_noise_canceller *c, const char *what)
 {
     if (!c || c->magic != MAGIC) { set_error("%s: not a noise canceller", what); return false; }
-    return true;
-}
-
-static bool pair_ok(const nvx_noise_canceller *c, const char *what, int pair, int lowest)
-{
-    if (pair < lowest || pair >= c->n_pairs) { set_error("%s: pair %d of %d", what, pair, c->n_pairs); return false; }
     return true;
 }
 
@@ -60,8 +51,7 @@ extern "C" void nvx_anc_config_default(nvx_anc_config *cfg)
 // --------------------------------------------------------------------------------------------------------------- plans
 static void release(nvx_noise_canceller *c)
 {
-    (void)hipFree(c->d_state[0]); (void)hipFree(c->d_state[1]); (void)hipFree(c->d_counters); (void)hipFree(c->d_records);
-    (void)hipFree(c->d_push_in); (void)hipFree(c->d_push_out);
+    c->state.release(); (void)hipFree(c->d_counters); (void)hipFree(c->d_records); c->push.release();
     c->timer.destroy();
     c->magic = 0;
     delete c;
@@ -71,15 +61,13 @@ static void release(nvx_noise_canceller *c)
 // reads.  The caller holds the lock, has selected the device and has waited for it.
 static int write_fresh_rows(nvx_noise_canceller *c, int first, int n)
 {
-    const size_t sw = (size_t)c->state_words, scalars = sw - NVX_ANC_STATE_SCALARS;
+    const size_t sw = c->state.words, scalars = sw - NVX_ANC_STATE_SCALARS;
     std::vector<int64_t> image;
-    for (int i = first; i < first + n;) {
-        int j = i;
-        while (j < first + n && c->parity[j] == c->parity[i]) j++;
+    for (int i = first, j; i < first + n; i = j) {
+        j = c->state.run_end(i, first + n);
         image.assign((size_t)(j - i) * sw, 0);
         for (int k = i; k < j; k++) image[(size_t)(k - i) * sw + scalars + NVX_ANC_ST_MODE] = c->mode[k];
-        HIP_TRY(hipMemcpy(c->row(i), image.data(), image.size() * sizeof(int64_t), hipMemcpyHostToDevice));
-        i = j;
+        HIP_TRY(hipMemcpy(c->state.row(i), image.data(), image.size() * sizeof(int64_t), hipMemcpyHostToDevice));
     }
     return NVX_OK;
 }
@@ -99,15 +87,12 @@ extern "C" int nvx_anc_create(const nvx_anc_config *cfg, nvx_noise_canceller **o
     int rc = select_device(cfg->device, NOUN);
     if (rc != NVX_OK) { release(c); return rc; }
     c->device = cfg->device; c->n_pairs = cfg->n_pairs; c->format = cfg->format; c->window_log2 = cfg->window_log2;
-    c->state_words = NVX_ANC_STATE_WORDS(cfg->window_log2);
-    c->consumed.assign(cfg->n_pairs, 0); c->samples.assign(cfg->n_pairs, 0);
-    c->parity.assign(cfg->n_pairs, 0); c->mode.assign(cfg->n_pairs, NVX_ANC_TRACK);
-    const size_t state_bytes = (size_t)cfg->n_pairs * c->state_words * sizeof(int64_t), counter_bytes = (size_t)cfg->n_pairs * 2 * sizeof(unsigned long long);
-    hipError_t e = hipMalloc((void **)&c->d_state[0], state_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_state[1], state_bytes);
+    c->consumed.assign(cfg->n_pairs, 0); c->samples.assign(cfg->n_pairs, 0); c->mode.assign(cfg->n_pairs, NVX_ANC_TRACK);
+    const size_t counter_bytes = (size_t)cfg->n_pairs * 2 * sizeof(unsigned long long);
+    hipError_t e = c->state.allocate(cfg->n_pairs, NVX_ANC_STATE_WORDS(cfg->window_log2));
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_counters, counter_bytes);
     if (e != hipSuccess) { set_error("%s: allocation failed: %s", what, hipGetErrorString(e)); release(c); return NVX_ERR_NOMEM; }
-    e = hipMemset(c->d_state[1], 0, state_bytes);
+    e = hipMemset(c->state.d[1], 0, c->state.bytes(cfg->n_pairs));
     if (e == hipSuccess) e = hipMemset(c->d_counters, 0, counter_bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { set_error("%s: clearing the state failed: %s", what, hipGetErrorString(e)); release(c); return NVX_ERR_HIP; }
@@ -136,8 +121,8 @@ extern "C" int nvx_anc_plan(nvx_noise_canceller *c, int *format, int *n_pairs, i
 // `pair` (-1: all) stands at `position` with nothing in front of it
 static int restart(nvx_noise_canceller *c, const char *what, int pair, uint64_t position)
 {
-    if (!pair_ok(c, what, pair, -1)) return NVX_ERR_ARG;
-    if (position >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
+    if (!row_ok(what, "pair", pair, -1, c->n_pairs)) return NVX_ERR_ARG;
+    if (!position_ok(what, position)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     int rc;
     if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
@@ -161,7 +146,7 @@ extern "C" int nvx_anc_debug_set_position(nvx_noise_canceller *c, int pair, uint
 extern "C" int nvx_anc_position(nvx_noise_canceller *c, int pair, uint64_t *consumed)
 {
     const char *what = "nvx_anc_position";
-    if (!valid(c, what) || !pair_ok(c, what, pair, 0)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !row_ok(what, "pair", pair, 0, c->n_pairs)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     if (consumed) *consumed = c->consumed[pair];
     return NVX_OK;
@@ -181,7 +166,7 @@ static int write_scalars(nvx_noise_canceller *c, int pair, int at, const int64_t
 extern "C" int nvx_anc_set(nvx_noise_canceller *c, int pair, int c_re, int c_im)
 {
     const char *what = "nvx_anc_set";
-    if (!valid(c, what) || !pair_ok(c, what, pair, -1)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !row_ok(what, "pair", pair, -1, c->n_pairs)) return NVX_ERR_ARG;
     if (c_re < -NVX_ANC_C_MAX || c_re > NVX_ANC_C_MAX || c_im < -NVX_ANC_C_MAX || c_im > NVX_ANC_C_MAX) {
         set_error("%s: (%d, %d): |c_re|, |c_im| <= %d", what, c_re, c_im, NVX_ANC_C_MAX);
         return NVX_ERR_ARG;
@@ -194,7 +179,7 @@ extern "C" int nvx_anc_set(nvx_noise_canceller *c, int pair, int c_re, int c_im)
 extern "C" int nvx_anc_set_mode(nvx_noise_canceller *c, int pair, int mode)
 {
     const char *what = "nvx_anc_set_mode";
-    if (!valid(c, what) || !pair_ok(c, what, pair, -1)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !row_ok(what, "pair", pair, -1, c->n_pairs)) return NVX_ERR_ARG;
     if (mode != NVX_ANC_TRACK && mode != NVX_ANC_HOLD) { set_error("%s: mode %d (NVX_ANC_TRACK or NVX_ANC_HOLD)", what, mode); return NVX_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     const int64_t v = mode;
@@ -207,15 +192,15 @@ extern "C" int nvx_anc_set_mode(nvx_noise_canceller *c, int pair, int mode)
 extern "C" int nvx_anc_get(nvx_noise_canceller *c, int pair, nvx_anc_status *out)
 {
     const char *what = "nvx_anc_get";
-    if (!valid(c, what) || !pair_ok(c, what, pair, 0)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !row_ok(what, "pair", pair, 0, c->n_pairs)) return NVX_ERR_ARG;
     if (!out) { set_error("%s: null argument", what); return NVX_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     int rc;
     if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
-    std::vector<int64_t> row((size_t)c->state_words);
+    std::vector<int64_t> row(c->state.words);
     unsigned long long counters[2] = { 0, 0 };
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(row.data(), c->row(pair), row.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(row.data(), c->state.row(pair),row.size() * sizeof(int64_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(counters, c->d_counters + 2 * (size_t)pair, sizeof counters, hipMemcpyDeviceToHost));
     const int W = 1 << c->window_log2;
     const int64_t *sc = row.data() + NVX_ANC_SUMS * W + NVX_ANC_SUMS;
@@ -231,17 +216,12 @@ extern "C" int nvx_anc_get(nvx_noise_canceller *c, int pair, nvx_anc_status *out
 
 extern "C" int nvx_anc_timing(nvx_noise_canceller *c, int enable)
 {
-    if (!valid(c, "nvx_anc_timing")) return NVX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->timer.enabled = enable != 0;
-    return NVX_OK;
+    return valid(c, "nvx_anc_timing") ? timing_enable(c->mu, c->timer, enable) : NVX_ERR_ARG;
 }
 
 extern "C" int nvx_anc_time_stats(nvx_noise_canceller *c, double *sum_ms, uint64_t *calls, int reset)
 {
-    if (!valid(c, "nvx_anc_time_stats")) return NVX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    return c->timer.collect(sum_ms, calls, reset);
+    return valid(c, "nvx_anc_time_stats") ? timing_collect(c->mu, c->timer, sum_ms, calls, reset) : NVX_ERR_ARG;
 }
 
 extern "C" int64_t nvx_anc_debug_last_launch(nvx_noise_canceller *c, int *chunks, int *tiles_per_chunk, int *records, int *form)
@@ -263,8 +243,7 @@ extern "C" int64_t nvx_anc_debug_last_launch(nvx_noise_canceller *c, int *chunks
 static int launch(nvx_noise_canceller *c, int first, int n, uint64_t consumed, int parity, const void *d_main, size_t pitch_main, const void *d_sense,
                   size_t pitch_sense, size_t n_in, uint32_t *d_out, size_t pitch_out, size_t out_first, hipStream_t s)
 {
-    // a workgroup per pair fills the chip from a few workgroups per CU on; below that a pair's tiles are spread out
-    const int wanted = n >= 1024 ? 1 : (NVX_ANC_TARGET_WORKGROUPS + n - 1) / n;
+    const int wanted = nvx_stream_wanted(n, NVX_ANC_TARGET_WORKGROUPS);
     nvx_anc_args a;
     int chunks = nvx_anc_fill_args(consumed, d_main, pitch_main, d_sense, pitch_sense, n_in, d_out, pitch_out, out_first, n, nullptr, nullptr, nullptr,
                                    nullptr, c->window_log2, wanted, &a);
@@ -280,9 +259,8 @@ static int launch(nvx_noise_canceller *c, int first, int n, uint64_t consumed, i
         }
         c->records_cap = records;
     }
-    chunks = nvx_anc_fill_args(consumed, d_main, pitch_main, d_sense, pitch_sense, n_in, d_out, pitch_out, out_first, n,
-                               c->d_state[parity] + (size_t)first * c->state_words, c->d_state[parity ^ 1] + (size_t)first * c->state_words, c->d_records,
-                               c->d_counters + 2 * (size_t)first, c->window_log2, wanted, &a);
+    chunks = nvx_anc_fill_args(consumed, d_main, pitch_main, d_sense, pitch_sense, n_in, d_out, pitch_out, out_first, n, c->state.in(first, parity),
+                               c->state.out(first, parity), c->d_records, c->d_counters + 2 * (size_t)first, c->window_log2, wanted, &a);
     nvx_event_timer::events ev;
     int rc;
     if ((rc = c->timer.begin(s, ev)) != NVX_OK) return rc;
@@ -291,7 +269,8 @@ static int launch(nvx_noise_canceller *c, int first, int n, uint64_t consumed, i
     c->last = { chunks, a.tiles_per_chunk, a.blocks, chunks > 1 ? 2 : 1 };
     c->kernel_launches += 2;
     if ((rc = c->timer.end(s, ev)) != NVX_OK) return rc;
-    for (int i = first; i < first + n; i++) { c->consumed[i] = consumed + n_in; c->samples[i] += n_in; c->parity[i] = (uint8_t)(parity ^ 1); }
+    for (int i = first; i < first + n; i++) { c->consumed[i] = consumed + n_in; c->samples[i] += n_in; }
+    c->state.flip(first, n, parity);
     return NVX_OK;
 }
 
@@ -312,14 +291,9 @@ extern "C" int nvx_anc_resident(nvx_noise_canceller *c, const void *d_main, size
         set_error("%s: bad argument (null pointer, an input not 16-byte aligned, output not 4-byte aligned, or more than 2^30 samples)", what);
         return NVX_ERR_ARG;
     }
-    for (int i = 1; i < c->n_pairs; i++)
-        if (c->consumed[i] != c->consumed[0]) {
-            set_error("%s: pair %d stands at %llu, pair 0 at %llu: all pairs of a call stand at the same position", what, i,
-                      (unsigned long long)c->consumed[i], (unsigned long long)c->consumed[0]);
-            return NVX_ERR_STATE;
-        }
+    if (!all_stand_together(what, "pair", c->consumed)) return NVX_ERR_STATE;
     const uint64_t consumed = c->consumed[0];
-    if ((consumed + n_in) >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
+    if (!position_ok(what, consumed + n_in)) return NVX_ERR_ARG;
     // every row's last sample read and last word written, in samples of its row (out_end) and in bytes of the whole operand
     const size_t rows = (size_t)c->n_pairs, bps = (size_t)BPS[c->format];
     size_t out_end, main_bytes, sense_bytes, out_bytes;
@@ -350,15 +324,8 @@ extern "C" int nvx_anc_resident(nvx_noise_canceller *c, const void *d_main, size
     if ((rc = check_device_span(d_sense, sense_bytes, what, "sense input")) != NVX_OK) return rc;
     if ((rc = check_device_span(d_out, out_bytes, what, "output")) != NVX_OK) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
-    // the state rows of pairs pushed one by one are brought to pair 0's parity
-    const int parity = c->parity[0];
-    for (int i = 1; i < c->n_pairs; i++)
-        if (c->parity[i] != parity) {
-            HIP_TRY(hipMemcpyAsync(c->d_state[parity] + (size_t)i * c->state_words, c->d_state[parity ^ 1] + (size_t)i * c->state_words,
-                                   (size_t)c->state_words * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-            c->parity[i] = (uint8_t)parity;
-        }
-    return launch(c, 0, c->n_pairs, consumed, parity, d_main, pitch_main, d_sense, pitch_sense, n_in, (uint32_t *)d_out, pitch_out, out_first, s);
+    if ((rc = c->state.align(nullptr, s)) != NVX_OK) return rc;
+    return launch(c, 0, c->n_pairs, consumed, c->state.parity[0], d_main, pitch_main, d_sense, pitch_sense, n_in, (uint32_t *)d_out, pitch_out, out_first, s);
 }
 
 extern "C" int nvx_anc_push(nvx_noise_canceller *c, int pair, const void *main_in, const void *sense_in, size_t n_in, int16_t *out_iq)
@@ -371,26 +338,17 @@ extern "C" int nvx_anc_push(nvx_noise_canceller *c, int pair, const void *main_i
         return NVX_ERR_ARG;
     }
     const uint64_t consumed = c->consumed[pair];
-    if ((consumed + n_in) >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
+    if (!position_ok(what, consumed + n_in)) return NVX_ERR_ARG;
     if (n_in == 0) return NVX_OK;
     int rc;
     if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
     // the sense row lies behind the main row, 16-byte aligned
     const size_t in_bytes = n_in * (size_t)BPS[c->format], row_bytes = (in_bytes + 15) & ~(size_t)15;
-    if (2 * row_bytes > c->push_in_cap) {
-        (void)hipFree(c->d_push_in); c->d_push_in = nullptr; c->push_in_cap = 0;
-        if (hipMalloc(&c->d_push_in, 2 * row_bytes) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, 2 * row_bytes); return NVX_ERR_NOMEM; }
-        c->push_in_cap = 2 * row_bytes;
-    }
-    if (n_in > c->push_out_cap) {
-        (void)hipFree(c->d_push_out); c->d_push_out = nullptr; c->push_out_cap = 0;
-        if (hipMalloc((void **)&c->d_push_out, n_in * 4) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, n_in * 4); return NVX_ERR_NOMEM; }
-        c->push_out_cap = n_in;
-    }
-    void *const d_sense = (char *)c->d_push_in + row_bytes;
-    HIP_TRY(hipMemcpy(c->d_push_in, main_in, in_bytes, hipMemcpyHostToDevice));
+    if ((rc = c->push.reserve(what, 2 * row_bytes, n_in)) != NVX_OK) return rc;
+    void *const d_sense = (char *)c->push.d_in + row_bytes;
+    HIP_TRY(hipMemcpy(c->push.d_in, main_in, in_bytes, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_sense, sense_in, in_bytes, hipMemcpyHostToDevice));
-    if ((rc = launch(c, pair, 1, consumed, c->parity[pair], c->d_push_in, n_in, d_sense, n_in, n_in, c->d_push_out, n_in, 0, nullptr)) != NVX_OK) return rc;
-    HIP_TRY(hipMemcpy(out_iq, c->d_push_out, n_in * 4, hipMemcpyDeviceToHost));     // waits for the null stream
+    if ((rc = launch(c, pair, 1, consumed, c->state.parity[pair], c->push.d_in, n_in, d_sense, n_in, n_in, c->push.d_out, n_in, 0, nullptr)) != NVX_OK) return rc;
+    HIP_TRY(hipMemcpy(out_iq, c->push.d_out, n_in * 4, hipMemcpyDeviceToHost));     // waits for the null stream
     return NVX_OK;
 }

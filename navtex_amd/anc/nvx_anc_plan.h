@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "navtex_amd_anc.h"
+#include "nvx_stream_plan.h"
 
 #define NVX_ANC_THREADS 256
 #define NVX_ANC_WAVES 4
@@ -71,16 +72,12 @@ static inline int nvx_anc_fill_args(uint64_t consumed, const void *d_main, size_
     a.state_in = state_in; a.state_out = state_out; a.records = records; a.counters = counters;
     a.n_in = (int)n_in;
     a.tiles = (int)((n_in + NVX_ANC_TILE - 1) / NVX_ANC_TILE);
-    if (wanted < 1) wanted = 1;
-    a.tiles_per_chunk = a.tiles ? (a.tiles + wanted - 1) / wanted : 1;
-    if (a.tiles_per_chunk < NVX_ANC_MIN_CHUNK_TILES) a.tiles_per_chunk = NVX_ANC_MIN_CHUNK_TILES;
-    if (a.tiles_per_chunk > a.tiles && a.tiles) a.tiles_per_chunk = a.tiles;
-    const int chunks = a.tiles ? (a.tiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk : 1;
+    const int chunks = nvx_stream_chunks(a.tiles, wanted, NVX_ANC_MIN_CHUNK_TILES, &a.tiles_per_chunk);
     a.off0 = (int)(consumed % NVX_ANC_BLOCK);
     a.blocks = n_in ? (int)(((uint64_t)a.off0 + n_in - 1) / NVX_ANC_BLOCK) + 1 : 0;
     a.slot0 = (int)((consumed / NVX_ANC_BLOCK) & ((1u << window_log2) - 1));
     a.window_log2 = window_log2; a.state_words = NVX_ANC_STATE_WORDS(window_log2);
-    a.out_vec = (((uintptr_t)d_out + (uintptr_t)out_first * 4) & 15) == 0 && (n_pairs == 1 || (pitch_out & 3) == 0);
+    a.out_vec = nvx_stream_rows_aligned16(d_out, pitch_out, out_first, n_pairs);
     *out = a;
     return chunks;
 }

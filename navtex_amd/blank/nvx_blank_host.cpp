@@ -20,14 +20,12 @@ struct nvx_blanker {
     std::mutex mu;
     int device = 0, n_streams = 0, format = 0;
     uint32_t thr_q8 = 0, hold = 0, floor = 0;
-    uint32_t *d_state[2] = { nullptr, nullptr };            // [n_streams][NVX_BLANK_STATE_WORDS], read and written alternately
+    nvx_state_rows<uint32_t> state;                         // [n_streams][NVX_BLANK_STATE_WORDS]
     unsigned long long *d_counters = nullptr;               // [n_streams][2]
     std::vector<uint64_t> consumed, samples;                // samples: since the last nvx_blank_stats(reset)
-    std::vector<uint8_t> parity;                            // which state row the stream's next launch reads
     std::vector<uint8_t> fresh;                             // reset since its last launch: that row is zeroed first
     nvx_event_timer timer;
-    void *d_push_in = nullptr; uint32_t *d_push_out = nullptr;
-    size_t push_in_cap = 0, push_out_cap = 0;
+    nvx_push_staging push;
     struct { int chunks, blocks_per_chunk, preroll_blocks, form; } last = {};
     int64_t kernel_launches = 0;
 };
@@ -50,8 +48,7 @@ extern "C" void nvx_blank_config_default(nvx_blank_config *cfg)
 // --------------------------------------------------------------------------------------------------------------- plans
 static void release(nvx_blanker *b)
 {
-    (void)hipFree(b->d_state[0]); (void)hipFree(b->d_state[1]); (void)hipFree(b->d_counters);
-    (void)hipFree(b->d_push_in); (void)hipFree(b->d_push_out);
+    b->state.release(); (void)hipFree(b->d_counters); b->push.release();
     b->timer.destroy();
     b->magic = 0;
     delete b;
@@ -78,15 +75,14 @@ extern "C" int nvx_blank_create(const nvx_blank_config *cfg, nvx_blanker **out)
     if (rc != NVX_OK) { release(b); return rc; }
     b->device = cfg->device; b->n_streams = cfg->n_streams; b->format = cfg->format;
     b->thr_q8 = cfg->thr_q8; b->hold = cfg->hold; b->floor = cfg->floor;
-    b->consumed.assign(cfg->n_streams, 0); b->samples.assign(cfg->n_streams, 0);
-    b->parity.assign(cfg->n_streams, 0); b->fresh.assign(cfg->n_streams, 0);
-    const size_t state_bytes = (size_t)cfg->n_streams * NVX_BLANK_STATE_WORDS * 4, counter_bytes = (size_t)cfg->n_streams * 2 * sizeof(unsigned long long);
-    hipError_t e = hipMalloc((void **)&b->d_state[0], state_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&b->d_state[1], state_bytes);
+    b->consumed.assign(cfg->n_streams, 0); b->samples.assign(cfg->n_streams, 0); b->fresh.assign(cfg->n_streams, 0);
+    const size_t counter_bytes = (size_t)cfg->n_streams * 2 * sizeof(unsigned long long);
+    hipError_t e = b->state.allocate(cfg->n_streams, NVX_BLANK_STATE_WORDS);
     if (e == hipSuccess) e = hipMalloc((void **)&b->d_counters, counter_bytes);
     if (e != hipSuccess) { set_error("%s: allocation failed: %s", what, hipGetErrorString(e)); release(b); return NVX_ERR_NOMEM; }
-    e = hipMemset(b->d_state[0], 0, state_bytes);
-    if (e == hipSuccess) e = hipMemset(b->d_state[1], 0, state_bytes);
+    const size_t state_bytes = b->state.bytes(cfg->n_streams);
+    e = hipMemset(b->state.d[0], 0, state_bytes);
+    if (e == hipSuccess) e = hipMemset(b->state.d[1], 0, state_bytes);
     if (e == hipSuccess) e = hipMemset(b->d_counters, 0, counter_bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { set_error("%s: clearing the state failed: %s", what, hipGetErrorString(e)); release(b); return NVX_ERR_HIP; }
@@ -116,8 +112,8 @@ extern "C" int nvx_blank_plan(nvx_blanker *b, int *format, int *n_streams, uint3
 // `stream` (-1: all) stands at `position` with nothing in front of it
 static int restart(nvx_blanker *b, const char *what, int stream, uint64_t position)
 {
-    if (stream < -1 || stream >= b->n_streams) { set_error("%s: stream %d of %d", what, stream, b->n_streams); return NVX_ERR_ARG; }
-    if (position >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
+    if (!row_ok(what, "stream", stream, -1, b->n_streams)) return NVX_ERR_ARG;
+    if (!position_ok(what, position)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(b->mu);
     for (int i = stream < 0 ? 0 : stream; i < (stream < 0 ? b->n_streams : stream + 1); i++) { b->consumed[i] = position; b->fresh[i] = 1; }
     return NVX_OK;
@@ -137,7 +133,7 @@ extern "C" int nvx_blank_position(nvx_blanker *b, int stream, uint64_t *consumed
 {
     const char *what = "nvx_blank_position";
     if (!valid(b, what)) return NVX_ERR_ARG;
-    if (stream < 0 || stream >= b->n_streams) { set_error("%s: stream %d of %d", what, stream, b->n_streams); return NVX_ERR_ARG; }
+    if (!row_ok(what, "stream", stream, 0, b->n_streams)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(b->mu);
     if (consumed) *consumed = b->consumed[stream];
     return NVX_OK;
@@ -147,7 +143,7 @@ extern "C" int nvx_blank_stats(nvx_blanker *b, int stream, uint64_t *samples, ui
 {
     const char *what = "nvx_blank_stats";
     if (!valid(b, what)) return NVX_ERR_ARG;
-    if (stream < 0 || stream >= b->n_streams) { set_error("%s: stream %d of %d", what, stream, b->n_streams); return NVX_ERR_ARG; }
+    if (!row_ok(what, "stream", stream, 0, b->n_streams)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(b->mu);
     int rc;
     if ((rc = select_device(b->device, NOUN)) != NVX_OK) return rc;
@@ -167,17 +163,12 @@ extern "C" int nvx_blank_stats(nvx_blanker *b, int stream, uint64_t *samples, ui
 
 extern "C" int nvx_blank_timing(nvx_blanker *b, int enable)
 {
-    if (!valid(b, "nvx_blank_timing")) return NVX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(b->mu);
-    b->timer.enabled = enable != 0;
-    return NVX_OK;
+    return valid(b, "nvx_blank_timing") ? timing_enable(b->mu, b->timer, enable) : NVX_ERR_ARG;
 }
 
 extern "C" int nvx_blank_time_stats(nvx_blanker *b, double *sum_ms, uint64_t *launches, int reset)
 {
-    if (!valid(b, "nvx_blank_time_stats")) return NVX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(b->mu);
-    return b->timer.collect(sum_ms, launches, reset);
+    return valid(b, "nvx_blank_time_stats") ? timing_collect(b->mu, b->timer, sum_ms, launches, reset) : NVX_ERR_ARG;
 }
 
 extern "C" int64_t nvx_blank_debug_last_launch(nvx_blanker *b, int *chunks, int *blocks_per_chunk, int *preroll_blocks, int *form)
@@ -204,16 +195,13 @@ static int launch(nvx_blanker *b, int first, int n, uint64_t consumed, int parit
         if (!b->fresh[i]) { i++; continue; }
         int j = i;
         while (j < first + n && b->fresh[j]) b->fresh[j++] = 0;
-        HIP_TRY(hipMemsetAsync(b->d_state[parity] + (size_t)i * NVX_BLANK_STATE_WORDS, 0, (size_t)(j - i) * NVX_BLANK_STATE_WORDS * 4, s));
+        HIP_TRY(hipMemsetAsync(b->state.in(i, parity), 0, b->state.bytes(j - i), s));
         i = j;
     }
-    // a workgroup per stream fills the chip from a few workgroups per CU on; below that a stream's tiles are spread out
-    const int wanted = n >= 1024 ? 1 : (NVX_BLANK_TARGET_WORKGROUPS + n - 1) / n;
     nvx_blank_args a;
-    const int chunks = nvx_blank_fill_args(consumed, d_in, pitch_in, n_in, d_out, pitch_out, out_first, n,
-                                           b->d_state[parity] + (size_t)first * NVX_BLANK_STATE_WORDS,
-                                           b->d_state[parity ^ 1] + (size_t)first * NVX_BLANK_STATE_WORDS, b->d_counters + 2 * (size_t)first,
-                                           b->thr_q8, b->hold, b->floor, wanted, &a);
+    const int chunks = nvx_blank_fill_args(consumed, d_in, pitch_in, n_in, d_out, pitch_out, out_first, n, b->state.in(first, parity),
+                                           b->state.out(first, parity), b->d_counters + 2 * (size_t)first, b->thr_q8, b->hold, b->floor,
+                                           nvx_stream_wanted(n, NVX_BLANK_TARGET_WORKGROUPS), &a);
     nvx_event_timer::events ev;
     int rc;
     if ((rc = b->timer.begin(s, ev)) != NVX_OK) return rc;
@@ -221,7 +209,8 @@ static int launch(nvx_blanker *b, int first, int n, uint64_t consumed, int parit
     b->last = { chunks, a.tiles_per_chunk * NVX_BLANK_WAVES, chunks > 1 ? NVX_BLANK_PREROLL_TILES * NVX_BLANK_WAVES : 0, chunks > 1 ? 2 : 1 };
     b->kernel_launches++;
     if ((rc = b->timer.end(s, ev)) != NVX_OK) return rc;
-    for (int i = first; i < first + n; i++) { b->consumed[i] = consumed + n_in; b->samples[i] += n_in; b->parity[i] = (uint8_t)(parity ^ 1); }
+    for (int i = first; i < first + n; i++) { b->consumed[i] = consumed + n_in; b->samples[i] += n_in; }
+    b->state.flip(first, n, parity);
     return NVX_OK;
 }
 
@@ -235,44 +224,18 @@ extern "C" int nvx_blank_resident(nvx_blanker *b, const void *d_in, size_t pitch
         set_error("%s: bad argument (null pointer, input not 16-byte aligned, output not 4-byte aligned, or more than 2^30 samples)", what);
         return NVX_ERR_ARG;
     }
-    for (int i = 1; i < b->n_streams; i++)
-        if (b->consumed[i] != b->consumed[0]) {
-            set_error("%s: stream %d stands at %llu, stream 0 at %llu: all streams of a call stand at the same position", what, i,
-                      (unsigned long long)b->consumed[i], (unsigned long long)b->consumed[0]);
-            return NVX_ERR_STATE;
-        }
+    if (!all_stand_together(what, "stream", b->consumed)) return NVX_ERR_STATE;
     const uint64_t consumed = b->consumed[0];
-    if ((consumed + n_in) >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
-    // every row's last sample read and last word written, in samples of its row (out_end) and in bytes of the whole operand
-    const size_t rows = (size_t)b->n_streams;
-    size_t out_end, in_bytes, out_bytes;
-    if (__builtin_add_overflow(out_first, n_in, &out_end) || !span_bytes(rows - 1, pitch_in, n_in, (size_t)BPS[b->format], &in_bytes) ||
-        !span_bytes(rows - 1, pitch_out, out_end, 4, &out_bytes)) {
-        set_error("%s: the span of %zu samples of %d streams at pitch %zu, or of as many words from %zu at pitch %zu, overflows", what, n_in,
-                  b->n_streams, pitch_in, out_first, pitch_out);
-        return NVX_ERR_ARG;
-    }
-    if ((rows > 1 && (n_in > pitch_in || ((pitch_in * (size_t)BPS[b->format]) & 15))) || (rows > 1 && out_end > pitch_out)) {
-        set_error("%s: %zu samples per stream at pitch %zu, words up to %zu at pitch %zu (a row must hold them, and input rows are 16-byte aligned)",
-                  what, n_in, pitch_in, out_end, pitch_out);
-        return NVX_ERR_ARG;
-    }
-    if (n_in == 0) return NVX_OK;
-    int rc;
+    if (!position_ok(what, consumed + n_in)) return NVX_ERR_ARG;
+    size_t in_bytes, out_bytes;
+    int rc = resident_spans(what, b->n_streams, (size_t)BPS[b->format], n_in, pitch_in, n_in, "as many", pitch_out, out_first, &in_bytes, &out_bytes);
+    if (rc != NVX_OK || n_in == 0) return rc;
     if ((rc = select_device(b->device, NOUN)) != NVX_OK) return rc;
     if ((rc = check_device_span(d_in, in_bytes, what, "input")) != NVX_OK) return rc;
     if ((rc = check_device_span(d_out, out_bytes, what, "output")) != NVX_OK) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
-    // the state rows of streams pushed one by one are brought to stream 0's parity
-    const int parity = b->parity[0];
-    for (int i = 1; i < b->n_streams; i++)
-        if (b->parity[i] != parity) {
-            if (!b->fresh[i])
-                HIP_TRY(hipMemcpyAsync(b->d_state[parity] + (size_t)i * NVX_BLANK_STATE_WORDS, b->d_state[parity ^ 1] + (size_t)i * NVX_BLANK_STATE_WORDS,
-                                       NVX_BLANK_STATE_WORDS * 4, hipMemcpyDeviceToDevice, s));
-            b->parity[i] = (uint8_t)parity;
-        }
-    return launch(b, 0, b->n_streams, consumed, parity, d_in, pitch_in, n_in, (uint32_t *)d_out, pitch_out, out_first, s);
+    if ((rc = b->state.align(b->fresh.data(), s)) != NVX_OK) return rc;     // a fresh row is zeroed by the launch
+    return launch(b, 0, b->n_streams, consumed, b->state.parity[0], d_in, pitch_in, n_in, (uint32_t *)d_out, pitch_out, out_first, s);
 }
 
 extern "C" int nvx_blank_push(nvx_blanker *b, int stream, const void *in, size_t n_in, int16_t *out_iq)
@@ -285,23 +248,14 @@ extern "C" int nvx_blank_push(nvx_blanker *b, int stream, const void *in, size_t
         return NVX_ERR_ARG;
     }
     const uint64_t consumed = b->consumed[stream];
-    if ((consumed + n_in) >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
+    if (!position_ok(what, consumed + n_in)) return NVX_ERR_ARG;
     if (n_in == 0) return NVX_OK;
     int rc;
     if ((rc = select_device(b->device, NOUN)) != NVX_OK) return rc;
     const size_t in_bytes = n_in * (size_t)BPS[b->format];
-    if (in_bytes > b->push_in_cap) {
-        (void)hipFree(b->d_push_in); b->d_push_in = nullptr; b->push_in_cap = 0;
-        if (hipMalloc(&b->d_push_in, in_bytes) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, in_bytes); return NVX_ERR_NOMEM; }
-        b->push_in_cap = in_bytes;
-    }
-    if (n_in > b->push_out_cap) {
-        (void)hipFree(b->d_push_out); b->d_push_out = nullptr; b->push_out_cap = 0;
-        if (hipMalloc((void **)&b->d_push_out, n_in * 4) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, n_in * 4); return NVX_ERR_NOMEM; }
-        b->push_out_cap = n_in;
-    }
-    HIP_TRY(hipMemcpy(b->d_push_in, in, in_bytes, hipMemcpyHostToDevice));
-    if ((rc = launch(b, stream, 1, consumed, b->parity[stream], b->d_push_in, n_in, n_in, b->d_push_out, n_in, 0, nullptr)) != NVX_OK) return rc;
-    HIP_TRY(hipMemcpy(out_iq, b->d_push_out, n_in * 4, hipMemcpyDeviceToHost));     // waits for the null stream
+    if ((rc = b->push.reserve(what, in_bytes, n_in)) != NVX_OK) return rc;
+    HIP_TRY(hipMemcpy(b->push.d_in, in, in_bytes, hipMemcpyHostToDevice));
+    if ((rc = launch(b, stream, 1, consumed, b->state.parity[stream], b->push.d_in, n_in, n_in, b->push.d_out, n_in, 0, nullptr)) != NVX_OK) return rc;
+    HIP_TRY(hipMemcpy(out_iq, b->push.d_out, n_in * 4, hipMemcpyDeviceToHost));     // waits for the null stream
     return NVX_OK;
 }

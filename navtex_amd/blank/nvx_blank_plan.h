@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "navtex_amd_blank.h"
+#include "nvx_stream_plan.h"
 
 #define NVX_BLANK_THREADS 256
 #define NVX_BLANK_WAVES 4
@@ -64,14 +65,10 @@ static inline int nvx_blank_fill_args(uint64_t consumed, const void *d_in, size_
     a.state_in = state_in; a.state_out = state_out; a.counters = counters;
     a.n_in = (int)n_in;
     a.tiles = (int)((n_in + NVX_BLANK_TILE - 1) / NVX_BLANK_TILE);
-    if (wanted < 1) wanted = 1;
-    a.tiles_per_chunk = a.tiles ? (a.tiles + wanted - 1) / wanted : 1;
-    if (a.tiles_per_chunk < NVX_BLANK_MIN_CHUNK_TILES) a.tiles_per_chunk = NVX_BLANK_MIN_CHUNK_TILES;
-    if (a.tiles_per_chunk > a.tiles && a.tiles) a.tiles_per_chunk = a.tiles;
-    const int chunks = a.tiles ? (a.tiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk : 1;
+    const int chunks = nvx_stream_chunks(a.tiles, wanted, NVX_BLANK_MIN_CHUNK_TILES, &a.tiles_per_chunk);
     a.off = NVX_BLANK_BLOCK - (int)(consumed % NVX_BLANK_BLOCK);
     a.hold = (int)hold; a.thr_q8 = thr_q8; a.floor = floor;
-    a.out_vec = (((uintptr_t)d_out + (uintptr_t)out_first * 4) & 15) == 0 && (n_streams == 1 || (pitch_out & 3) == 0);
+    a.out_vec = nvx_stream_rows_aligned16(d_out, pitch_out, out_first, n_streams);
     *out = a;
     return chunks;
 }

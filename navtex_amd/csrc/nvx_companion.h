@@ -1,6 +1,8 @@
-// nvx_companion.h -- what the host sides of the companion libraries (the scan, the resampler, the down-converter bank)
-// have in common: the thread's error text, HIP_TRY, the device and span checks, HIP-event timing.  Internal, and all of
-// it static: every library compiles its own copy and they share no state.  The main library has nvx_handle.h instead.
+// nvx_companion.h -- what the host sides of the companion libraries have in common.  For all of them: the thread's error
+// text, HIP_TRY, the device and span checks, HIP-event timing.  For the four that keep the sample rate (the blanker, the IQ
+// corrector, the real-input converter, the noise canceller), below those: the position checks, the state rows read and
+// written alternately, a push's staging buffers.  Internal, and all of it static: every library compiles its own copy and
+// they share no state.  The main library has nvx_handle.h instead.
 #ifndef NVX_COMPANION_H
 #define NVX_COMPANION_H
 
@@ -9,6 +11,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <mutex>
 #include <utility>
 #include <vector>
 
@@ -122,6 +125,129 @@ struct nvx_event_timer {
         for (auto &p : pool) { (void)hipEventDestroy(p.first); (void)hipEventDestroy(p.second); }
         pool.clear(); pending.clear();
     }
+};
+
+// the bodies of a library's *_timing and *_time_stats; mu is the lock of what the timer belongs to
+static inline int timing_enable(std::mutex &mu, nvx_event_timer &t, int enable)
+{
+    std::lock_guard<std::mutex> lk(mu);
+    t.enabled = enable != 0;
+    return NVX_OK;
+}
+
+static inline int timing_collect(std::mutex &mu, nvx_event_timer &t, double *sum_ms, uint64_t *n, int reset)
+{
+    std::lock_guard<std::mutex> lk(mu);
+    return t.collect(sum_ms, n, reset);
+}
+
+// ------------------------------------------------------------------------- the same-rate companions: rows at positions
+static inline bool position_ok(const char *what, uint64_t position)
+{
+    if (position >> 62) set_error("%s: the position passes 2^62", what);
+    return !(position >> 62);
+}
+
+// row i of n, or -1 (all of them) where `lowest` says so; `noun` is what the library calls a row: "stream", "pair"
+static inline bool row_ok(const char *what, const char *noun, int i, int lowest, int n)
+{
+    if (i < lowest || i >= n) set_error("%s: %s %d of %d", what, noun, i, n);
+    return i >= lowest && i < n;
+}
+
+// row i stands where row 0 does
+static inline bool stands_with_first(const char *what, const char *noun, const std::vector<uint64_t> &at, size_t i)
+{
+    if (at[i] != at[0])
+        set_error("%s: %s %zu stands at %llu, %s 0 at %llu: all %ss of a call stand at the same position", what, noun, i, (unsigned long long)at[i], noun,
+                  (unsigned long long)at[0], noun);
+    return at[i] == at[0];
+}
+
+static inline bool all_stand_together(const char *what, const char *noun, const std::vector<uint64_t> &at)
+{
+    for (size_t i = 1; i < at.size(); i++)
+        if (!stands_with_first(what, noun, at, i)) return false;
+    return true;
+}
+
+// The spans of a resident call with one input: n_in samples of bps bytes read of each of n_rows streams at pitch_in, n_out
+// words (`as_many` as samples, for the sentence) written of each from out_first on at pitch_out.  in_bytes and out_bytes
+// reach from the operand's first byte to the last row's last sample read and last word written.
+static inline int resident_spans(const char *what, int n_rows, size_t bps, size_t n_in, size_t pitch_in, size_t n_out, const char *as_many,
+                                 size_t pitch_out, size_t out_first, size_t *in_bytes, size_t *out_bytes)
+{
+    const size_t rows = (size_t)n_rows;
+    size_t out_end;
+    if (__builtin_add_overflow(out_first, n_out, &out_end) || !span_bytes(rows - 1, pitch_in, n_in, bps, in_bytes) ||
+        !span_bytes(rows - 1, pitch_out, out_end, 4, out_bytes)) {
+        set_error("%s: the span of %zu samples of %d streams at pitch %zu, or of %s words from %zu at pitch %zu, overflows", what, n_in, n_rows, pitch_in,
+                  as_many, out_first, pitch_out);
+        return NVX_ERR_ARG;
+    }
+    if (rows > 1 && (n_in > pitch_in || ((pitch_in * bps) & 15) || out_end > pitch_out)) {
+        set_error("%s: %zu samples per stream at pitch %zu, words up to %zu at pitch %zu (a row must hold them, and input rows are 16-byte aligned)",
+                  what, n_in, pitch_in, out_end, pitch_out);
+        return NVX_ERR_ARG;
+    }
+    return NVX_OK;
+}
+
+// The state rows of a plan, [rows][words] of W twice over: a launch reads a row in one and writes it in the other, and
+// `parity` says which of the two row i's next launch reads.  The caller holds the plan's lock.
+template <typename W> struct nvx_state_rows {
+    W *d[2] = { nullptr, nullptr };
+    size_t words = 0;
+    std::vector<uint8_t> parity;
+
+    size_t bytes(size_t rows) const { return rows * words * sizeof(W); }
+    hipError_t allocate(int rows, size_t row_words)
+    {
+        words = row_words; parity.assign(rows, 0);
+        const hipError_t e = hipMalloc((void **)&d[0], bytes(rows));
+        return e != hipSuccess ? e : hipMalloc((void **)&d[1], bytes(rows));
+    }
+    void release() { (void)hipFree(d[0]); (void)hipFree(d[1]); }
+    W *row(int i) const { return d[parity[i]] + (size_t)i * words; }
+    // what a launch over the rows from `first` on, which stand at parity p, reads and writes
+    W *in(int first, int p) const { return d[p] + (size_t)first * words; }
+    W *out(int first, int p) const { return d[p ^ 1] + (size_t)first * words; }
+    void flip(int first, int n, int p) { for (int i = first; i < first + n; i++) parity[i] = (uint8_t)(p ^ 1); }
+    // where the run of rows from i on that lie side by side (at one parity) ends, `end` at the latest
+    int run_end(int i, int end) const { int j = i; while (j < end && parity[j] == parity[i]) j++; return j; }
+    // Rows pushed one by one are brought to row 0's parity, on s, for a launch over all of them; a row that `skip` marks
+    // holds nothing worth the copy.
+    int align(const uint8_t *skip, hipStream_t s)
+    {
+        const int p = parity[0];
+        for (size_t i = 1; i < parity.size(); i++)
+            if (parity[i] != p) {
+                if (!skip || !skip[i]) HIP_TRY(hipMemcpyAsync(d[p] + i * words, d[p ^ 1] + i * words, bytes(1), hipMemcpyDeviceToDevice, s));
+                parity[i] = (uint8_t)p;
+            }
+        return NVX_OK;
+    }
+};
+
+// A push's input and output on the device; they grow to the largest push.
+struct nvx_push_staging {
+    void *d_in = nullptr; uint32_t *d_out = nullptr;
+    size_t in_cap = 0, out_cap = 0;     // bytes, words
+
+    static int grow(const char *what, void **p, size_t *cap, size_t units, size_t unit_bytes)
+    {
+        if (units <= *cap) return NVX_OK;
+        (void)hipFree(*p); *p = nullptr; *cap = 0;
+        if (hipMalloc(p, units * unit_bytes) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, units * unit_bytes); return NVX_ERR_NOMEM; }
+        *cap = units;
+        return NVX_OK;
+    }
+    int reserve(const char *what, size_t in_bytes, size_t out_words)
+    {
+        const int rc = grow(what, &d_in, &in_cap, in_bytes, 1);
+        return rc != NVX_OK ? rc : grow(what, (void **)&d_out, &out_cap, out_words, 4);
+    }
+    void release() { (void)hipFree(d_in); (void)hipFree(d_out); }
 };
 
 #endif

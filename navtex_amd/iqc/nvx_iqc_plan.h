@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "navtex_amd_iqc.h"
+#include "nvx_stream_plan.h"
 
 #define NVX_IQC_THREADS 256
 #define NVX_IQC_WAVES 4
@@ -69,16 +70,12 @@ static inline int nvx_iqc_fill_args(uint64_t consumed, const void *d_in, size_t 
     a.state_in = state_in; a.state_out = state_out; a.records = records; a.counters = counters;
     a.n_in = (int)n_in;
     a.tiles = (int)((n_in + NVX_IQC_TILE - 1) / NVX_IQC_TILE);
-    if (wanted < 1) wanted = 1;
-    a.tiles_per_chunk = a.tiles ? (a.tiles + wanted - 1) / wanted : 1;
-    if (a.tiles_per_chunk < NVX_IQC_MIN_CHUNK_TILES) a.tiles_per_chunk = NVX_IQC_MIN_CHUNK_TILES;
-    if (a.tiles_per_chunk > a.tiles && a.tiles) a.tiles_per_chunk = a.tiles;
-    const int chunks = a.tiles ? (a.tiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk : 1;
+    const int chunks = nvx_stream_chunks(a.tiles, wanted, NVX_IQC_MIN_CHUNK_TILES, &a.tiles_per_chunk);
     a.off0 = (int)(consumed % NVX_IQC_BLOCK);
     a.blocks = n_in ? (int)(((uint64_t)a.off0 + n_in - 1) / NVX_IQC_BLOCK) + 1 : 0;
     a.slot0 = (int)((consumed / NVX_IQC_BLOCK) & ((1u << window_log2) - 1));
     a.window_log2 = window_log2; a.state_words = NVX_IQC_STATE_WORDS(window_log2);
-    a.out_vec = (((uintptr_t)d_out + (uintptr_t)out_first * 4) & 15) == 0 && (n_streams == 1 || (pitch_out & 3) == 0);
+    a.out_vec = nvx_stream_rows_aligned16(d_out, pitch_out, out_first, n_streams);
     *out = a;
     return chunks;
 }

@@ -19,29 +19,19 @@ struct nvx_real_converter {
     uint32_t magic = MAGIC;
     std::mutex mu;
     int device = 0, n_streams = 0, format = 0, invert = 0;
-    uint32_t *d_state[2] = { nullptr, nullptr };            // [n_streams][NVX_REAL_STATE_WORDS], read and written alternately
+    nvx_state_rows<uint32_t> state;                         // [n_streams][NVX_REAL_STATE_WORDS]
     std::vector<uint64_t> consumed;                         // samples the kernel has taken: even
-    std::vector<uint8_t> parity;                            // which state row the stream's next launch reads
     std::vector<uint8_t> held;                              // 1: a push left an odd sample, in `sample`
     std::vector<uint32_t> sample;                           // its bytes
     nvx_event_timer timer;
-    void *d_push_in = nullptr; uint32_t *d_push_out = nullptr;
-    size_t push_in_cap = 0, push_out_cap = 0;               // bytes, words
+    nvx_push_staging push;
     struct { int chunks, tiles_per_chunk, form; } last = {};
     int64_t kernel_launches = 0;
-
-    uint32_t *row(int stream) { return d_state[parity[stream]] + (size_t)stream * NVX_REAL_STATE_WORDS; }
 };
 
 static bool valid(const nvx_real_converter *c, const char *what)
 {
     if (!c || c->magic != MAGIC) { set_error("%s: not a real-input converter", what); return false; }
-    return true;
-}
-
-static bool stream_ok(const nvx_real_converter *c, const char *what, int stream, int lowest)
-{
-    if (stream < lowest || stream >= c->n_streams) { set_error("%s: stream %d of %d", what, stream, c->n_streams); return false; }
     return true;
 }
 
@@ -65,7 +55,7 @@ extern "C" int nvx_real_taps(int16_t *taps, int cap, int *K, int *S)
 // --------------------------------------------------------------------------------------------------------------- plans
 static void release(nvx_real_converter *c)
 {
-    (void)hipFree(c->d_state[0]); (void)hipFree(c->d_state[1]); (void)hipFree(c->d_push_in); (void)hipFree(c->d_push_out);
+    c->state.release(); c->push.release();
     c->timer.destroy();
     c->magic = 0;
     delete c;
@@ -86,14 +76,12 @@ extern "C" int nvx_real_create(const nvx_real_config *cfg, nvx_real_converter **
     int rc = select_device(cfg->device, NOUN);
     if (rc != NVX_OK) { release(c); return rc; }
     c->device = cfg->device; c->n_streams = cfg->n_streams; c->format = cfg->format; c->invert = cfg->invert;
-    c->consumed.assign(cfg->n_streams, 0); c->parity.assign(cfg->n_streams, 0);
-    c->held.assign(cfg->n_streams, 0); c->sample.assign(cfg->n_streams, 0);
-    const size_t state_bytes = (size_t)cfg->n_streams * NVX_REAL_STATE_WORDS * sizeof(uint32_t);
-    hipError_t e = hipMalloc((void **)&c->d_state[0], state_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_state[1], state_bytes);
+    c->consumed.assign(cfg->n_streams, 0); c->held.assign(cfg->n_streams, 0); c->sample.assign(cfg->n_streams, 0);
+    hipError_t e = c->state.allocate(cfg->n_streams, NVX_REAL_STATE_WORDS);
     if (e != hipSuccess) { set_error("%s: allocation failed: %s", what, hipGetErrorString(e)); release(c); return NVX_ERR_NOMEM; }
-    e = hipMemset(c->d_state[0], 0, state_bytes);
-    if (e == hipSuccess) e = hipMemset(c->d_state[1], 0, state_bytes);
+    const size_t state_bytes = c->state.bytes(cfg->n_streams);
+    e = hipMemset(c->state.d[0], 0, state_bytes);
+    if (e == hipSuccess) e = hipMemset(c->state.d[1], 0, state_bytes);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { set_error("%s: clearing the state failed: %s", what, hipGetErrorString(e)); release(c); return NVX_ERR_HIP; }
     *out = c;
@@ -120,18 +108,16 @@ extern "C" int nvx_real_plan(nvx_real_converter *c, int *format, int *n_streams,
 // `stream` (-1: all) stands at sample `position` with silence in front of it and no sample held
 static int restart(nvx_real_converter *c, const char *what, int stream, uint64_t position)
 {
-    if (!stream_ok(c, what, stream, -1)) return NVX_ERR_ARG;
+    if (!row_ok(what, "stream", stream, -1, c->n_streams)) return NVX_ERR_ARG;
     if ((position >> 62) || (position & 1)) { set_error("%s: position %llu (even, below 2^62)", what, (unsigned long long)position); return NVX_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     int rc;
     if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     const int first = stream < 0 ? 0 : stream, n = stream < 0 ? c->n_streams : 1;
-    for (int i = first; i < first + n;) {                   // runs of streams whose rows lie side by side
-        int j = i;
-        while (j < first + n && c->parity[j] == c->parity[i]) j++;
-        HIP_TRY(hipMemset(c->row(i), 0, (size_t)(j - i) * NVX_REAL_STATE_WORDS * sizeof(uint32_t)));
-        i = j;
+    for (int i = first, j; i < first + n; i = j) {          // runs of streams whose rows lie side by side
+        j = c->state.run_end(i, first + n);
+        HIP_TRY(hipMemset(c->state.row(i), 0, c->state.bytes(j - i)));
     }
     HIP_TRY(hipDeviceSynchronize());
     for (int i = first; i < first + n; i++) { c->consumed[i] = position; c->held[i] = 0; }
@@ -151,7 +137,7 @@ extern "C" int nvx_real_debug_set_position(nvx_real_converter *c, int stream, ui
 extern "C" int nvx_real_position(nvx_real_converter *c, int stream, uint64_t *consumed, uint64_t *produced)
 {
     const char *what = "nvx_real_position";
-    if (!valid(c, what) || !stream_ok(c, what, stream, 0)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !row_ok(what, "stream", stream, 0, c->n_streams)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     if (consumed) *consumed = c->consumed[stream] + c->held[stream];
     if (produced) *produced = c->consumed[stream] / 2;
@@ -160,17 +146,12 @@ extern "C" int nvx_real_position(nvx_real_converter *c, int stream, uint64_t *co
 
 extern "C" int nvx_real_timing(nvx_real_converter *c, int enable)
 {
-    if (!valid(c, "nvx_real_timing")) return NVX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->timer.enabled = enable != 0;
-    return NVX_OK;
+    return valid(c, "nvx_real_timing") ? timing_enable(c->mu, c->timer, enable) : NVX_ERR_ARG;
 }
 
 extern "C" int nvx_real_time_stats(nvx_real_converter *c, double *sum_ms, uint64_t *calls, int reset)
 {
-    if (!valid(c, "nvx_real_time_stats")) return NVX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    return c->timer.collect(sum_ms, calls, reset);
+    return valid(c, "nvx_real_time_stats") ? timing_collect(c->mu, c->timer, sum_ms, calls, reset) : NVX_ERR_ARG;
 }
 
 extern "C" int64_t nvx_real_debug_last_launch(nvx_real_converter *c, int *chunks, int *tiles_per_chunk, int *form)
@@ -191,12 +172,9 @@ extern "C" int64_t nvx_real_debug_last_launch(nvx_real_converter *c, int *chunks
 static int launch(nvx_real_converter *c, int first, int n, uint64_t consumed, int parity, const void *d_in, size_t pitch_in, size_t n_in,
                   uint32_t *d_out, size_t pitch_out, size_t out_first, hipStream_t s)
 {
-    // a workgroup per stream fills the chip from a few workgroups per CU on; below that a stream's tiles are spread out
-    const int wanted = n >= 1024 ? 1 : (NVX_REAL_TARGET_WORKGROUPS + n - 1) / n;
     nvx_real_args a;
-    const int chunks = nvx_real_fill_args(consumed, d_in, pitch_in, n_in, d_out, pitch_out, out_first, n,
-                                          c->d_state[parity] + (size_t)first * NVX_REAL_STATE_WORDS,
-                                          c->d_state[parity ^ 1] + (size_t)first * NVX_REAL_STATE_WORDS, c->invert, wanted, &a);
+    const int chunks = nvx_real_fill_args(consumed, d_in, pitch_in, n_in, d_out, pitch_out, out_first, n, c->state.in(first, parity),
+                                          c->state.out(first, parity), c->invert, nvx_stream_wanted(n, NVX_REAL_TARGET_WORKGROUPS), &a);
     nvx_event_timer::events ev;
     int rc;
     if ((rc = c->timer.begin(s, ev)) != NVX_OK) return rc;
@@ -204,7 +182,8 @@ static int launch(nvx_real_converter *c, int first, int n, uint64_t consumed, in
     c->last = { chunks, a.tiles_per_chunk, chunks > 1 ? 2 : 1 };
     c->kernel_launches += 1;
     if ((rc = c->timer.end(s, ev)) != NVX_OK) return rc;
-    for (int i = first; i < first + n; i++) { c->consumed[i] = consumed + n_in; c->parity[i] = (uint8_t)(parity ^ 1); }
+    for (int i = first; i < first + n; i++) c->consumed[i] = consumed + n_in;
+    c->state.flip(first, n, parity);
     return NVX_OK;
 }
 
@@ -223,43 +202,19 @@ extern "C" int nvx_real_resident(nvx_real_converter *c, const void *d_in, size_t
             set_error("%s: stream %d holds the odd sample of a push: push one more sample, or reset it", what, i);
             return NVX_ERR_STATE;
         }
-        if (c->consumed[i] != c->consumed[0]) {
-            set_error("%s: stream %d stands at %llu, stream 0 at %llu: all streams of a call stand at the same position", what, i,
-                      (unsigned long long)c->consumed[i], (unsigned long long)c->consumed[0]);
-            return NVX_ERR_STATE;
-        }
+        if (!stands_with_first(what, "stream", c->consumed, i)) return NVX_ERR_STATE;
     }
     const uint64_t consumed = c->consumed[0];
-    if ((consumed + n_in) >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
-    // every row's last sample read and last word written, in samples of its row (out_end) and in bytes of the whole operand
-    const size_t rows = (size_t)c->n_streams, n_out = n_in / 2;
-    size_t out_end, in_bytes, out_bytes;
-    if (__builtin_add_overflow(out_first, n_out, &out_end) || !span_bytes(rows - 1, pitch_in, n_in, (size_t)BPS[c->format], &in_bytes) ||
-        !span_bytes(rows - 1, pitch_out, out_end, 4, &out_bytes)) {
-        set_error("%s: the span of %zu samples of %d streams at pitch %zu, or of half as many words from %zu at pitch %zu, overflows", what, n_in,
-                  c->n_streams, pitch_in, out_first, pitch_out);
-        return NVX_ERR_ARG;
-    }
-    if ((rows > 1 && (n_in > pitch_in || ((pitch_in * (size_t)BPS[c->format]) & 15))) || (rows > 1 && out_end > pitch_out)) {
-        set_error("%s: %zu samples per stream at pitch %zu, words up to %zu at pitch %zu (a row must hold them, and input rows are 16-byte aligned)",
-                  what, n_in, pitch_in, out_end, pitch_out);
-        return NVX_ERR_ARG;
-    }
-    if (n_in == 0) return NVX_OK;
-    int rc;
+    if (!position_ok(what, consumed + n_in)) return NVX_ERR_ARG;
+    size_t in_bytes, out_bytes;
+    int rc = resident_spans(what, c->n_streams, (size_t)BPS[c->format], n_in, pitch_in, n_in / 2, "half as many", pitch_out, out_first, &in_bytes, &out_bytes);
+    if (rc != NVX_OK || n_in == 0) return rc;
     if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
     if ((rc = check_device_span(d_in, in_bytes, what, "input")) != NVX_OK) return rc;
     if ((rc = check_device_span(d_out, out_bytes, what, "output")) != NVX_OK) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
-    // the state rows of streams pushed one by one are brought to stream 0's parity
-    const int parity = c->parity[0];
-    for (int i = 1; i < c->n_streams; i++)
-        if (c->parity[i] != parity) {
-            HIP_TRY(hipMemcpyAsync(c->d_state[parity] + (size_t)i * NVX_REAL_STATE_WORDS, c->d_state[parity ^ 1] + (size_t)i * NVX_REAL_STATE_WORDS,
-                                   NVX_REAL_STATE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-            c->parity[i] = (uint8_t)parity;
-        }
-    return launch(c, 0, c->n_streams, consumed, parity, d_in, pitch_in, n_in, (uint32_t *)d_out, pitch_out, out_first, s);
+    if ((rc = c->state.align(nullptr, s)) != NVX_OK) return rc;
+    return launch(c, 0, c->n_streams, consumed, c->state.parity[0], d_in, pitch_in, n_in, (uint32_t *)d_out, pitch_out, out_first, s);
 }
 
 extern "C" int nvx_real_push(nvx_real_converter *c, int stream, const void *in, size_t n_in, int16_t *out_iq, size_t cap_samples, size_t *n_out)
@@ -274,28 +229,19 @@ extern "C" int nvx_real_push(nvx_real_converter *c, int stream, const void *in, 
     const size_t bps = (size_t)BPS[c->format], have = n_in + c->held[stream], use = have & ~(size_t)1, words = use / 2;
     if (words > cap_samples) { set_error("%s: %zu outputs, room for %zu", what, words, cap_samples); return NVX_ERR_ARG; }
     const uint64_t consumed = c->consumed[stream];
-    if ((consumed + have) >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
+    if (!position_ok(what, consumed + have)) return NVX_ERR_ARG;
     *n_out = 0;
     if (use) {
         int rc;
         if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
         const size_t in_bytes = use * bps;
-        if (in_bytes > c->push_in_cap) {
-            (void)hipFree(c->d_push_in); c->d_push_in = nullptr; c->push_in_cap = 0;
-            if (hipMalloc(&c->d_push_in, in_bytes) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, in_bytes); return NVX_ERR_NOMEM; }
-            c->push_in_cap = in_bytes;
-        }
-        if (words > c->push_out_cap) {
-            (void)hipFree(c->d_push_out); c->d_push_out = nullptr; c->push_out_cap = 0;
-            if (hipMalloc((void **)&c->d_push_out, words * 4) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, words * 4); return NVX_ERR_NOMEM; }
-            c->push_out_cap = words;
-        }
+        if ((rc = c->push.reserve(what, in_bytes, words)) != NVX_OK) return rc;
         // the held sample goes in front
         const size_t front = c->held[stream] ? bps : 0;
-        if (front) HIP_TRY(hipMemcpy(c->d_push_in, &c->sample[stream], bps, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy((char *)c->d_push_in + front, in, in_bytes - front, hipMemcpyHostToDevice));
-        if ((rc = launch(c, stream, 1, consumed, c->parity[stream], c->d_push_in, use, use, c->d_push_out, words, 0, nullptr)) != NVX_OK) return rc;
-        HIP_TRY(hipMemcpy(out_iq, c->d_push_out, words * 4, hipMemcpyDeviceToHost));    // waits for the null stream
+        if (front) HIP_TRY(hipMemcpy(c->push.d_in, &c->sample[stream], bps, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy((char *)c->push.d_in + front, in, in_bytes - front, hipMemcpyHostToDevice));
+        if ((rc = launch(c, stream, 1, consumed, c->state.parity[stream], c->push.d_in, use, use, c->push.d_out, words, 0, nullptr)) != NVX_OK) return rc;
+        HIP_TRY(hipMemcpy(out_iq, c->push.d_out, words * 4, hipMemcpyDeviceToHost));    // waits for the null stream
         *n_out = words;
     }
     if (have & 1) {                                         // the last sample waits for its partner

@@ -9,6 +9,7 @@
 
 #include "navtex_amd_real.h"
 #include "nvx_real_taps.h"
+#include "nvx_stream_plan.h"
 
 #define NVX_REAL_THREADS 256
 #define NVX_REAL_WAVES 4
@@ -65,15 +66,11 @@ static inline int nvx_real_fill_args(uint64_t consumed, const void *d_in, size_t
     a.state_in = state_in; a.state_out = state_out;
     a.n = (int)(n_in / 2);
     a.tiles = (int)((n_in / 2 + NVX_REAL_TILE - 1) / NVX_REAL_TILE);
-    if (wanted < 1) wanted = 1;
-    a.tiles_per_chunk = a.tiles ? (a.tiles + wanted - 1) / wanted : 1;
-    if (a.tiles_per_chunk < NVX_REAL_MIN_CHUNK_TILES) a.tiles_per_chunk = NVX_REAL_MIN_CHUNK_TILES;
-    if (a.tiles_per_chunk > a.tiles && a.tiles) a.tiles_per_chunk = a.tiles;
-    const int chunks = a.tiles ? (a.tiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk : 1;
+    const int chunks = nvx_stream_chunks(a.tiles, wanted, NVX_REAL_MIN_CHUNK_TILES, &a.tiles_per_chunk);
     /* output i of the call is the stream's m = consumed / 2 + i, and m - K has the parity of m + K */
     a.par = (int)((consumed / 2 + NVX_REAL_K) & 1);
     a.invert = invert;
-    a.out_vec = (((uintptr_t)d_out + (uintptr_t)out_first * 4) & 15) == 0 && (n_streams == 1 || (pitch_out & 3) == 0);
+    a.out_vec = nvx_stream_rows_aligned16(d_out, pitch_out, out_first, n_streams);
     *out = a;
     return chunks;
 }
