@@ -1,8 +1,9 @@
 // nvx_companion.h -- what the host sides of the companion libraries have in common.  For all of them: the thread's error
-// text, HIP_TRY, the device and span checks, HIP-event timing.  For the four that keep the sample rate (the blanker, the IQ
-// corrector, the real-input converter, the noise canceller), below those: the position checks, the state rows read and
-// written alternately, a push's staging buffers.  Internal, and all of it static: every library compiles its own copy and
-// they share no state.  The main library has nvx_handle.h instead.
+// text, HIP_TRY, the device and span checks, HIP-event timing.  For those that carry rows of streams from call to call (the
+// blanker, the IQ corrector, the real-input converter, the noise canceller, and the rate changers: the resampler, the
+// down-converter bank, the narrowband interpolator, the channel tap), below those: the position and row checks, the state rows
+// read and written alternately, a push's staging buffers.  Internal, and all of it static: every library compiles its own
+// copy and they share no state.  The main library has nvx_handle.h instead.
 #ifndef NVX_COMPANION_H
 #define NVX_COMPANION_H
 
@@ -141,14 +142,14 @@ static inline int timing_collect(std::mutex &mu, nvx_event_timer &t, double *sum
     return t.collect(sum_ms, n, reset);
 }
 
-// ------------------------------------------------------------------------- the same-rate companions: rows at positions
+// ----------------------------------------------------------------------------------------------------- rows at positions
 static inline bool position_ok(const char *what, uint64_t position)
 {
     if (position >> 62) set_error("%s: the position passes 2^62", what);
     return !(position >> 62);
 }
 
-// row i of n, or -1 (all of them) where `lowest` says so; `noun` is what the library calls a row: "stream", "pair"
+// row i of n, or -1 (all of them) where `lowest` says so; `noun` is what the library calls a row: "stream", "pair", "input"
 static inline bool row_ok(const char *what, const char *noun, int i, int lowest, int n)
 {
     if (i < lowest || i >= n) set_error("%s: %s %d of %d", what, noun, i, n);
@@ -229,7 +230,8 @@ template <typename W> struct nvx_state_rows {
     }
 };
 
-// A push's input and output on the device; they grow to the largest push.
+// A push's input and output on the device; they grow to the largest push.  A failed allocation leaves nothing behind in the
+// runtime's last error: the library's next launch reports its own.
 struct nvx_push_staging {
     void *d_in = nullptr; uint32_t *d_out = nullptr;
     size_t in_cap = 0, out_cap = 0;     // bytes, words
@@ -238,7 +240,7 @@ struct nvx_push_staging {
     {
         if (units <= *cap) return NVX_OK;
         (void)hipFree(*p); *p = nullptr; *cap = 0;
-        if (hipMalloc(p, units * unit_bytes) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, units * unit_bytes); return NVX_ERR_NOMEM; }
+        if (hipMalloc(p, units * unit_bytes) != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of %zu bytes failed", what, units * unit_bytes); return NVX_ERR_NOMEM; }
         *cap = units;
         return NVX_OK;
     }

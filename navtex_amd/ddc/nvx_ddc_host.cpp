@@ -1,7 +1,7 @@
 // nvx_ddc_host.cpp -- the down-converter bank's entry points (include/navtex_amd_ddc.h): the grid rule, the config
-// checks, the carried shifts, the choice of launch shape.  The plan, its carried positions, the launch arithmetic, the
-// checks of a call and HIP-event timing are the resampler's (navtex_amd/resample/nvx_rs_host.h), compiled into this library
-// as its design (nvx_resample_design.c) is: code, not a library.  The library stands alone: it shares no state with the
+// checks, the carried shifts, the choice of launch shape.  The plan, its carried positions, the launch arithmetic and the
+// checks of a call are the resampler's (navtex_amd/resample/nvx_rs_host.h), compiled into this library as its design
+// (nvx_resample_design.c) is: code, not a library.  HIP-event timing is nvx_companion.h's.  The library stands alone: it shares no state with the
 // other three.
 #include <cmath>
 #include <cstring>
@@ -205,7 +205,7 @@ extern "C" int nvx_ddc_debug_set_position(nvx_ddc *d, int input, uint64_t consum
     if ((rc = select_device(d->p.device, d->p.library)) != NVX_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     for (int i = input < 0 ? 0 : input; i < (input < 0 ? d->p.n_inputs : input + 1); i++) {
-        for (int row = 0; row < 2; row++) HIP_TRY(hipMemset(d->p.d_hist[row] + (size_t)i * d->p.hist_pitch, 0, (size_t)d->p.hist_pitch * 4));     // silence in front
+        for (int row = 0; row < 2; row++) HIP_TRY(hipMemset(d->p.hist.in(i, row), 0, d->p.hist.bytes(1)));     // silence in front
         d->p.consumed[i] = consumed;
     }
     HIP_TRY(hipDeviceSynchronize());
@@ -219,12 +219,12 @@ extern "C" int nvx_ddc_position(nvx_ddc *d, int input, uint64_t *consumed, uint6
 
 extern "C" int nvx_ddc_timing(nvx_ddc *d, int enable)
 {
-    return valid(d, "nvx_ddc_timing") ? nvx_rs_timing(d->p, enable) : NVX_ERR_ARG;
+    return valid(d, "nvx_ddc_timing") ? timing_enable(d->p.mu, d->p.timer, enable) : NVX_ERR_ARG;
 }
 
 extern "C" int nvx_ddc_time_stats(nvx_ddc *d, double *sum_ms, uint64_t *launches, int reset)
 {
-    return valid(d, "nvx_ddc_time_stats") ? nvx_rs_time_stats(d->p, sum_ms, launches, reset) : NVX_ERR_ARG;
+    return valid(d, "nvx_ddc_time_stats") ? timing_collect(d->p.mu, d->p.timer, sum_ms, launches, reset) : NVX_ERR_ARG;
 }
 
 extern "C" int64_t nvx_ddc_debug_last_launch(nvx_ddc *d, int *K, int *tiles, int *tiles_per_chunk, int *chunks, int *slices,
@@ -325,8 +325,8 @@ extern "C" int nvx_ddc_push(nvx_ddc *d, int input, const void *in, size_t n_in, 
     if (n_in == 0) { if (n_out) *n_out = 0; return NVX_OK; }
     const size_t row_words = c.outs ? c.outs : 1;
     if ((rc = nvx_rs_push_stage(p, what, in, n_in, row_words * d->n_slices)) != NVX_OK) return rc;
-    if ((rc = launch(d, input, 1, c, p.d_push_in, n_in, n_in, p.d_push_out, row_words, 0, nullptr)) != NVX_OK) return rc;
-    if (c.outs) HIP_TRY(hipMemcpy2D(out_iq, cap_samples * 4, p.d_push_out, row_words * 4, c.outs * 4, (size_t)d->n_slices, hipMemcpyDeviceToHost));     // waits for the null stream
+    if ((rc = launch(d, input, 1, c, p.push.d_in, n_in, n_in, p.push.d_out, row_words, 0, nullptr)) != NVX_OK) return rc;
+    if (c.outs) HIP_TRY(hipMemcpy2D(out_iq, cap_samples * 4, p.push.d_out, row_words * 4, c.outs * 4, (size_t)d->n_slices, hipMemcpyDeviceToHost));     // waits for the null stream
     else HIP_TRY(hipStreamSynchronize(nullptr));
     if (n_out) *n_out = c.outs;
     return NVX_OK;

@@ -1,6 +1,7 @@
 // nvx_narrow_host.cpp -- the narrowband interpolator's entry points (include/navtex_amd_narrow.h): the design without a
-// device, the config checks, the plan with its tap table, carried positions and state rows, the checks of a call, and a
-// push's staging.  The launch arithmetic is nvx_narrow_plan.h's.  The library stands alone: it shares no state with any other.
+// device, the config checks, the plan with its tap table and carried positions, and the checks of a call.  The state rows,
+// a push's staging, the row and position checks and the timing bodies are nvx_companion.h's, the launch arithmetic
+// nvx_narrow_plan.h's.  The library stands alone: it shares no state with any other.
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -21,12 +22,10 @@ struct nvx_nb_interpolator {
     int device = 0, n_streams = 0, format = 0, kind = 0;
     nvx_nb_args shape = {};                                 // L, M, T and what follows from them
     uint32_t *d_table = nullptr;
-    uint32_t *d_state[2] = { nullptr, nullptr };            // [n_streams][NVX_NB_STATE_WORDS], read and written alternately
+    nvx_state_rows<uint32_t> state;                         // [n_streams][NVX_NB_STATE_WORDS]
     std::vector<uint64_t> consumed;
-    std::vector<uint8_t> parity;                            // which state row the stream's next launch reads
     nvx_event_timer timer;
-    void *d_push_in = nullptr; uint32_t *d_push_out = nullptr;
-    size_t push_in_cap = 0, push_out_cap = 0;               // bytes, words
+    nvx_push_staging push;
     struct { int chunks, tiles_per_chunk, form; size_t lds_bytes; } last = {};
     int64_t kernel_launches = 0;
 
@@ -36,12 +35,6 @@ struct nvx_nb_interpolator {
 static bool valid(const nvx_nb_interpolator *c, const char *what)
 {
     if (!c || c->magic != MAGIC) { set_error("%s: not a narrowband interpolator", what); return false; }
-    return true;
-}
-
-static bool stream_ok(const nvx_nb_interpolator *c, const char *what, int stream, int lowest)
-{
-    if (stream < lowest || stream >= c->n_streams) { set_error("%s: stream %d of %d", what, stream, c->n_streams); return false; }
     return true;
 }
 
@@ -76,7 +69,8 @@ extern "C" void nvx_nb_config_default(nvx_nb_config *cfg)
 // --------------------------------------------------------------------------------------------------------------- plans
 static void release(nvx_nb_interpolator *c)
 {
-    (void)hipFree(c->d_table); (void)hipFree(c->d_state[0]); (void)hipFree(c->d_state[1]); (void)hipFree(c->d_push_in); (void)hipFree(c->d_push_out);
+    (void)hipFree(c->d_table);
+    c->state.release(); c->push.release();
     c->timer.destroy();
     c->magic = 0;
     delete c;
@@ -107,20 +101,19 @@ extern "C" int nvx_nb_create(const nvx_nb_config *cfg, nvx_nb_interpolator **out
     if (rc != NVX_OK) { release(c); return rc; }
     c->device = cfg->device; c->n_streams = cfg->n_streams; c->format = cfg->format; c->kind = cfg->kind;
     nvx_nb_fill_shape(L, M, T, &c->shape);
-    c->consumed.assign(cfg->n_streams, 0); c->parity.assign(cfg->n_streams, 0);
+    c->consumed.assign(cfg->n_streams, 0);
     // the table as the kernel reads it: rows of Tp int16, zeros in front of the phase's taps reversed
     const int Tp = 8 * c->shape.tq, row = 8 * c->shape.row_quads;
     std::vector<int16_t> table((size_t)L * row, 0);
     for (int r = 0; r < L; r++)
         for (int t = 0; t < T; t++) table[(size_t)r * row + (Tp - 1 - t)] = taps[(size_t)r * T + t];
-    const size_t table_bytes = table.size() * sizeof(int16_t), state_bytes = (size_t)cfg->n_streams * NVX_NB_STATE_WORDS * sizeof(uint32_t);
+    const size_t table_bytes = table.size() * sizeof(int16_t);
     hipError_t e = hipMalloc((void **)&c->d_table, table_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_state[0], state_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_state[1], state_bytes);
+    if (e == hipSuccess) e = c->state.allocate(cfg->n_streams, NVX_NB_STATE_WORDS);
     if (e != hipSuccess) { set_error("%s: allocation failed: %s", what, hipGetErrorString(e)); release(c); return NVX_ERR_NOMEM; }
     e = hipMemcpy(c->d_table, table.data(), table_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(c->d_state[0], 0, state_bytes);
-    if (e == hipSuccess) e = hipMemset(c->d_state[1], 0, state_bytes);
+    if (e == hipSuccess) e = hipMemset(c->state.d[0], 0, c->state.bytes(cfg->n_streams));
+    if (e == hipSuccess) e = hipMemset(c->state.d[1], 0, c->state.bytes(cfg->n_streams));
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { set_error("%s: filling the table and the state failed: %s", what, hipGetErrorString(e)); release(c); return NVX_ERR_HIP; }
     nvx_nb_prepare();
@@ -151,16 +144,15 @@ extern "C" int nvx_nb_plan(nvx_nb_interpolator *c, int *L, int *M, int *T, int *
 // `stream` (-1: all) stands at input sample `position` with silence in front of it
 static int restart(nvx_nb_interpolator *c, const char *what, int stream, uint64_t position)
 {
-    if (!stream_ok(c, what, stream, -1)) return NVX_ERR_ARG;
+    if (!row_ok(what, "stream", stream, -1, c->n_streams)) return NVX_ERR_ARG;
     if (position >> 62) { set_error("%s: position %llu (below 2^62)", what, (unsigned long long)position); return NVX_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     int rc;
     if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     const int first = stream < 0 ? 0 : stream, n = stream < 0 ? c->n_streams : 1;
-    const size_t bytes = (size_t)n * NVX_NB_STATE_WORDS * sizeof(uint32_t);
-    HIP_TRY(hipMemset(c->d_state[0] + (size_t)first * NVX_NB_STATE_WORDS, 0, bytes));
-    HIP_TRY(hipMemset(c->d_state[1] + (size_t)first * NVX_NB_STATE_WORDS, 0, bytes));
+    HIP_TRY(hipMemset(c->state.in(first, 0), 0, c->state.bytes(n)));
+    HIP_TRY(hipMemset(c->state.in(first, 1), 0, c->state.bytes(n)));
     HIP_TRY(hipDeviceSynchronize());
     for (int i = first; i < first + n; i++) c->consumed[i] = position;
     return NVX_OK;
@@ -179,7 +171,7 @@ extern "C" int nvx_nb_debug_set_position(nvx_nb_interpolator *c, int stream, uin
 extern "C" int nvx_nb_position(nvx_nb_interpolator *c, int stream, uint64_t *consumed, uint64_t *produced)
 {
     const char *what = "nvx_nb_position";
-    if (!valid(c, what) || !stream_ok(c, what, stream, 0)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !row_ok(what, "stream", stream, 0, c->n_streams)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     if (consumed) *consumed = c->consumed[stream];
     if (produced) *produced = nvx_nb_outputs_after(c->consumed[stream], c->shape.L, c->shape.M);
@@ -188,17 +180,12 @@ extern "C" int nvx_nb_position(nvx_nb_interpolator *c, int stream, uint64_t *con
 
 extern "C" int nvx_nb_timing(nvx_nb_interpolator *c, int enable)
 {
-    if (!valid(c, "nvx_nb_timing")) return NVX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->timer.enabled = enable != 0;
-    return NVX_OK;
+    return valid(c, "nvx_nb_timing") ? timing_enable(c->mu, c->timer, enable) : NVX_ERR_ARG;
 }
 
 extern "C" int nvx_nb_time_stats(nvx_nb_interpolator *c, double *sum_ms, uint64_t *calls, int reset)
 {
-    if (!valid(c, "nvx_nb_time_stats")) return NVX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    return c->timer.collect(sum_ms, calls, reset);
+    return valid(c, "nvx_nb_time_stats") ? timing_collect(c->mu, c->timer, sum_ms, calls, reset) : NVX_ERR_ARG;
 }
 
 extern "C" int64_t nvx_nb_debug_last_launch(nvx_nb_interpolator *c, int *chunks, int *tiles_per_chunk, int *form, int *windows, int *parts,
@@ -222,7 +209,7 @@ extern "C" int64_t nvx_nb_debug_last_launch(nvx_nb_interpolator *c, int *chunks,
 static bool call_outputs(const nvx_nb_interpolator *c, const char *what, uint64_t consumed, size_t n_in, size_t *outs)
 {
     if (n_in > NVX_NB_MAX_IN) { set_error("%s: %zu samples (at most 2^30 per call)", what, n_in); return false; }
-    if ((consumed + n_in) >> 62) { set_error("%s: the position passes 2^62", what); return false; }
+    if (!position_ok(what, consumed + n_in)) return false;
     const uint64_t n = (uint64_t)(nvx_nb_outputs_after_wide(consumed + n_in, c->shape.L, c->shape.M) - nvx_nb_outputs_after_wide(consumed, c->shape.L, c->shape.M));
     if (n >> 31) { set_error("%s: %zu samples give %llu outputs: a call's outputs stay below 2^31", what, n_in, (unsigned long long)n); return false; }
     *outs = (size_t)n;
@@ -234,12 +221,9 @@ static bool call_outputs(const nvx_nb_interpolator *c, const char *what, uint64_
 static int launch(nvx_nb_interpolator *c, int first, int n, uint64_t consumed, int parity, const void *d_in, size_t pitch_in, size_t n_in,
                   uint32_t *d_out, size_t pitch_out, size_t out_first, hipStream_t s)
 {
-    // a workgroup per stream fills the chip from a few workgroups per CU on; below that a stream's tiles are spread out
-    const int wanted = n >= 1024 ? 1 : (NVX_NB_TARGET_WORKGROUPS + n - 1) / n;
     nvx_nb_args a = c->shape;
-    const int chunks = nvx_nb_fill_args(consumed, d_in, pitch_in, n_in, d_out, pitch_out, out_first,
-                                        c->d_state[parity] + (size_t)first * NVX_NB_STATE_WORDS,
-                                        c->d_state[parity ^ 1] + (size_t)first * NVX_NB_STATE_WORDS, c->d_table, wanted, &a);
+    const int chunks = nvx_nb_fill_args(consumed, d_in, pitch_in, n_in, d_out, pitch_out, out_first, c->state.in(first, parity),
+                                        c->state.out(first, parity), c->d_table, nvx_stream_wanted(n, NVX_NB_TARGET_WORKGROUPS), &a);
     nvx_event_timer::events ev;
     int rc;
     if ((rc = c->timer.begin(s, ev)) != NVX_OK) return rc;
@@ -247,7 +231,8 @@ static int launch(nvx_nb_interpolator *c, int first, int n, uint64_t consumed, i
     c->last = { chunks, a.tiles_per_chunk, chunks > 1 ? 2 : 1, nvx_nb_lds_bytes(&a) };
     c->kernel_launches += 1;
     if ((rc = c->timer.end(s, ev)) != NVX_OK) return rc;
-    for (int i = first; i < first + n; i++) { c->consumed[i] = consumed + n_in; c->parity[i] = (uint8_t)(parity ^ 1); }
+    for (int i = first; i < first + n; i++) c->consumed[i] = consumed + n_in;
+    c->state.flip(first, n, parity);
     return NVX_OK;
 }
 
@@ -261,12 +246,7 @@ extern "C" int nvx_nb_resident(nvx_nb_interpolator *c, const void *d_in, size_t 
         set_error("%s: bad argument (null pointer, input not 16-byte aligned, or output not 4-byte aligned)", what);
         return NVX_ERR_ARG;
     }
-    for (int i = 1; i < c->n_streams; i++)
-        if (c->consumed[i] != c->consumed[0]) {
-            set_error("%s: stream %d stands at %llu, stream 0 at %llu: all streams of a call stand at the same position", what, i,
-                      (unsigned long long)c->consumed[i], (unsigned long long)c->consumed[0]);
-            return NVX_ERR_STATE;
-        }
+    if (!all_stand_together(what, "stream", c->consumed)) return NVX_ERR_STATE;
     const uint64_t consumed = c->consumed[0];
     size_t outs;
     if (!call_outputs(c, what, consumed, n_in, &outs)) return NVX_ERR_ARG;
@@ -292,14 +272,8 @@ extern "C" int nvx_nb_resident(nvx_nb_interpolator *c, const void *d_in, size_t 
     if ((rc = check_device_span(d_out, out_bytes, what, "output")) != NVX_OK) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     // the state rows of streams pushed one by one are brought to stream 0's parity
-    const int parity = c->parity[0];
-    for (int i = 1; i < c->n_streams; i++)
-        if (c->parity[i] != parity) {
-            HIP_TRY(hipMemcpyAsync(c->d_state[parity] + (size_t)i * NVX_NB_STATE_WORDS, c->d_state[parity ^ 1] + (size_t)i * NVX_NB_STATE_WORDS,
-                                   NVX_NB_STATE_WORDS * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
-            c->parity[i] = (uint8_t)parity;
-        }
-    return launch(c, 0, c->n_streams, consumed, parity, d_in, pitch_in, n_in, (uint32_t *)d_out, pitch_out, out_first, s);
+    if ((rc = c->state.align(nullptr, s)) != NVX_OK) return rc;
+    return launch(c, 0, c->n_streams, consumed, c->state.parity[0], d_in, pitch_in, n_in, (uint32_t *)d_out, pitch_out, out_first, s);
 }
 
 extern "C" int nvx_nb_push(nvx_nb_interpolator *c, int stream, const void *in, size_t n_in, int16_t *out_iq, size_t cap_samples, size_t *n_out)
@@ -320,18 +294,9 @@ extern "C" int nvx_nb_push(nvx_nb_interpolator *c, int stream, const void *in, s
     int rc;
     if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
     const size_t in_bytes = n_in * c->bps();
-    if (in_bytes > c->push_in_cap) {
-        (void)hipFree(c->d_push_in); c->d_push_in = nullptr; c->push_in_cap = 0;
-        if (hipMalloc(&c->d_push_in, in_bytes) != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of %zu bytes failed", what, in_bytes); return NVX_ERR_NOMEM; }
-        c->push_in_cap = in_bytes;
-    }
-    if (outs > c->push_out_cap) {
-        (void)hipFree(c->d_push_out); c->d_push_out = nullptr; c->push_out_cap = 0;
-        if (hipMalloc((void **)&c->d_push_out, outs * 4) != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of %zu bytes failed", what, outs * 4); return NVX_ERR_NOMEM; }
-        c->push_out_cap = outs;
-    }
-    HIP_TRY(hipMemcpy(c->d_push_in, in, in_bytes, hipMemcpyHostToDevice));
-    if ((rc = launch(c, stream, 1, consumed, c->parity[stream], c->d_push_in, n_in, n_in, c->d_push_out, outs, 0, nullptr)) != NVX_OK) return rc;
-    HIP_TRY(hipMemcpy(out_iq, c->d_push_out, outs * 4, hipMemcpyDeviceToHost));     // waits for the null stream
+    if ((rc = c->push.reserve(what, in_bytes, outs)) != NVX_OK) return rc;
+    HIP_TRY(hipMemcpy(c->push.d_in, in, in_bytes, hipMemcpyHostToDevice));
+    if ((rc = launch(c, stream, 1, consumed, c->state.parity[stream], c->push.d_in, n_in, n_in, c->push.d_out, outs, 0, nullptr)) != NVX_OK) return rc;
+    HIP_TRY(hipMemcpy(out_iq, c->push.d_out, outs * 4, hipMemcpyDeviceToHost));     // waits for the null stream
     return NVX_OK;
 }

@@ -9,6 +9,8 @@
 #include <stdint.h>
 
 #include "navtex_amd_narrow.h"
+#include "nvx_polyphase_design.h"
+#include "nvx_stream_plan.h"
 
 #define NVX_NB_THREADS 256
 #define NVX_NB_MAX_T 32                     /* taps per phase the kernel has registers for */
@@ -30,11 +32,8 @@ int nvx_nb_plan_numbers(uint32_t num, uint32_t den, int *L, int *M, int *T, cons
 /* the L * T taps, phase-major taps[r * T + t] */
 int nvx_nb_plan_taps(int L, int T, int16_t *taps, const char **why);
 /* ceil(n * L / M) for n < 2^63, in full and as its low 64 bits (exact for n below 2^54: L / M is below 2^10) */
-static inline unsigned __int128 nvx_nb_outputs_after_wide(uint64_t n, int L, int M)
-{
-    return ((unsigned __int128)n * (unsigned)L + (unsigned)(M - 1)) / (unsigned)M;
-}
-static inline uint64_t nvx_nb_outputs_after(uint64_t n, int L, int M) { return (uint64_t)nvx_nb_outputs_after_wide(n, L, M); }
+static inline unsigned __int128 nvx_nb_outputs_after_wide(uint64_t n, int L, int M) { return nvx_pp_outputs_after_wide(n, L, M); }
+static inline uint64_t nvx_nb_outputs_after(uint64_t n, int L, int M) { return nvx_pp_outputs_after(n, L, M); }
 
 /* For tests: the shape of the plan's last call -- workgroups per stream, tiles a full workgroup walks, the form (1: one
  * workgroup per stream, 2: a stream spread over several), the windows (input samples) of a tile, the threads that share a
@@ -154,14 +153,11 @@ static inline int nvx_nb_fill_args(uint64_t consumed, const void *d_in, size_t p
     a->n_out = (int)(nvx_nb_outputs_after_wide(consumed + n_in, a->L, a->M) - before);
     a->e0 = (uint32_t)(before * (unsigned)a->M - (unsigned __int128)consumed * (unsigned)a->L);
     a->tiles = (int)((n_in + (size_t)a->windows - 1) / (size_t)a->windows);
-    if (wanted < 1) wanted = 1;
     if (wanted > NVX_NB_MAX_CHUNKS) wanted = NVX_NB_MAX_CHUNKS;
-    a->tiles_per_chunk = (a->tiles + wanted - 1) / wanted;
-    if (a->tiles_per_chunk < NVX_NB_MIN_CHUNK_TILES) a->tiles_per_chunk = NVX_NB_MIN_CHUNK_TILES;
-    if (a->tiles_per_chunk > a->tiles) a->tiles_per_chunk = a->tiles;
+    const int chunks = nvx_stream_chunks(a->tiles, wanted, NVX_NB_MIN_CHUNK_TILES, &a->tiles_per_chunk);
     const uint64_t step = (uint64_t)a->tiles_per_chunk * (uint64_t)a->windows * (uint64_t)a->L;
     a->chunk_di = (uint32_t)(step / (uint64_t)a->M); a->chunk_dr = (uint32_t)(step % (uint64_t)a->M);
-    return (a->tiles + a->tiles_per_chunk - 1) / a->tiles_per_chunk;
+    return chunks;
 }
 
 #if defined(__HIPCC__)

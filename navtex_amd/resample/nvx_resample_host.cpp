@@ -1,7 +1,7 @@
 // nvx_resample_host.cpp -- the resampler's entry points (include/navtex_amd_resample.h): the design without a device,
-// the config checks, the choice of kernel form.  The plan, its carried positions, the launch arithmetic, the checks of a
-// call and HIP-event timing are nvx_rs_host.h's, which the down-converter bank compiles too.  The library stands alone: it
-// shares no state with libnavtex_amd.so.
+// the config checks, the choice of kernel form.  The plan, its carried positions, the launch arithmetic and the checks of a
+// call are nvx_rs_host.h's, which the down-converter bank compiles too; HIP-event timing is nvx_companion.h's.  The library
+// stands alone: it shares no state with libnavtex_amd.so.
 #include <cstring>
 #include <new>
 
@@ -127,12 +127,12 @@ extern "C" int nvx_resample_set_form(nvx_resampler *r, int form)
 
 extern "C" int nvx_resample_timing(nvx_resampler *r, int enable)
 {
-    return valid(r, "nvx_resample_timing") ? nvx_rs_timing(r->p, enable) : NVX_ERR_ARG;
+    return valid(r, "nvx_resample_timing") ? timing_enable(r->p.mu, r->p.timer, enable) : NVX_ERR_ARG;
 }
 
 extern "C" int nvx_resample_time_stats(nvx_resampler *r, double *sum_ms, uint64_t *launches, int reset)
 {
-    return valid(r, "nvx_resample_time_stats") ? nvx_rs_time_stats(r->p, sum_ms, launches, reset) : NVX_ERR_ARG;
+    return valid(r, "nvx_resample_time_stats") ? timing_collect(r->p.mu, r->p.timer, sum_ms, launches, reset) : NVX_ERR_ARG;
 }
 
 extern "C" int64_t nvx_resample_debug_last_launch(nvx_resampler *r, int *K, int *tiles, int *tiles_per_chunk, int *chunks,
@@ -212,8 +212,8 @@ extern "C" int nvx_resample_push(nvx_resampler *r, int stream, const void *in, s
     if (n_in == 0) { if (n_out) *n_out = 0; return NVX_OK; }
     const size_t out_words = c.outs ? c.outs : 1;
     if ((rc = nvx_rs_push_stage(p, what, in, n_in, out_words)) != NVX_OK) return rc;
-    if ((rc = launch(r, stream, 1, c, p.d_push_in, n_in, n_in, p.d_push_out, out_words, 0, nullptr)) != NVX_OK) return rc;
-    if (c.outs) HIP_TRY(hipMemcpy(out_iq, p.d_push_out, c.outs * 4, hipMemcpyDeviceToHost));     // waits for the null stream
+    if ((rc = launch(r, stream, 1, c, p.push.d_in, n_in, n_in, p.push.d_out, out_words, 0, nullptr)) != NVX_OK) return rc;
+    if (c.outs) HIP_TRY(hipMemcpy(out_iq, p.push.d_out, c.outs * 4, hipMemcpyDeviceToHost));     // waits for the null stream
     else HIP_TRY(hipStreamSynchronize(nullptr));
     if (n_out) *n_out = c.outs;
     return NVX_OK;

@@ -1,7 +1,8 @@
 // nvx_rs_host.h -- the polyphase plan the resampler (nvx_resample_host.cpp) and the down-converter bank
 // (navtex_amd/ddc/nvx_ddc_host.cpp) both run: the plan's numbers and tap table, its carried positions and history rows,
-// the launch arithmetic of nvx_rs_args, the checks of a resident call and the staging of a push.  Internal, and all of it
-// static: each library compiles its own copy and they share no state.
+// the launch arithmetic of nvx_rs_args, the checks of a resident call and the staging of a push.  The rows, the staging, the
+// row and position checks and the timing bodies are nvx_companion.h's, the chunk split nvx_stream_plan.h's.  Internal, and all
+// of it static: each library compiles its own copy and they share no state.
 //
 // A plan has `n_inputs` input rows (the resampler's streams, the bank's inputs).  A call writes `out_rows` output rows:
 // one per input row in the resampler, one per slice of each in the bank.
@@ -13,6 +14,7 @@
 
 #include "nvx_companion.h"
 #include "nvx_resample_plan.h"
+#include "nvx_stream_plan.h"
 
 static const int NVX_RS_BPS[4] = { 4, 2, 2, 8 };          // bytes per input sample, by format
 static const int NVX_RS_TARGET_WORKGROUPS = 2048;         // a row's tiles are spread over chunks until the grid has about this many
@@ -23,15 +25,14 @@ struct nvx_rs_plan {
     std::mutex mu;
     int device = 0, n_inputs = 0, format = 0;
     uint32_t rate = 0;
-    int L = 0, M = 0, T = 0, Tp = 0, row_dw = 0, tap_dw = 0, K = 0, hist_pitch = 0;
+    int L = 0, M = 0, T = 0, Tp = 0, row_dw = 0, tap_dw = 0, K = 0;
     bool taps_in_lds = false;
     uint32_t dq = 0, dr = 0;
-    uint32_t *d_taps = nullptr, *d_hist[2] = { nullptr, nullptr };
+    uint32_t *d_taps = nullptr;
+    nvx_state_rows<uint32_t> hist;               // [n_inputs][words]: the T - 1 converted samples in front of an input's next call
     std::vector<uint64_t> consumed;
-    std::vector<uint8_t> parity;                 // which history row the input's next launch reads
     nvx_event_timer timer;
-    void *d_push_in = nullptr; uint32_t *d_push_out = nullptr;     // a push's staging, grown on demand
-    size_t push_in_cap = 0, push_out_cap = 0;
+    nvx_push_staging push;
 };
 
 // ------------------------------------------------------------------------------------------------------ without a device
@@ -44,7 +45,7 @@ static inline bool nvx_rs_plan_shape(nvx_rs_plan &p, int L, int M, int T)
     p.tap_dw = (NVX_RS_ALIGN * L * p.row_dw + 3) & ~3;
     p.taps_in_lds = (size_t)p.tap_dw * 4 <= NVX_RS_TAPS_LDS_MAX;
     p.dq = (uint32_t)(NVX_RS_THREADS * (uint64_t)M / L); p.dr = (uint32_t)(NVX_RS_THREADS * (uint64_t)M % L);
-    p.hist_pitch = (T - 1 + 3) & ~3;
+    p.hist.words = (size_t)((T - 1 + 3) & ~3);
     // the largest tile whose input span fits the planes: (256 K - 1) M / L + 1 samples between its first and last window
     // end, T - 1 in front, up to 7 + 15 of rounding to groups
     for (p.K = NVX_RS_MAX_K; p.K > 1; p.K--)
@@ -60,10 +61,9 @@ static inline int nvx_rs_fill_args(const nvx_rs_plan &p, int first_input, uint64
 {
     nvx_rs_args a{};
     a.in = d_in; a.pitch_in = pitch_in; a.out = d_out; a.pitch_out = pitch_out; a.out_first = out_first;
-    a.hist_in = p.d_hist[parity] + (size_t)first_input * p.hist_pitch;
-    a.hist_out = p.d_hist[parity ^ 1] + (size_t)first_input * p.hist_pitch;
+    a.hist_in = p.hist.in(first_input, parity); a.hist_out = p.hist.out(first_input, parity);
     a.taps = p.d_taps;
-    a.hist_pitch = p.hist_pitch; a.hist_valid = consumed > 0;
+    a.hist_pitch = (int)p.hist.words; a.hist_valid = consumed > 0;
     a.n_in = (int)n_in; a.n_out = (int)n_out;
     a.L = p.L; a.M = p.M; a.T = p.T; a.Tp = p.Tp; a.row_dw = p.row_dw; a.tap_dw = p.tap_dw; a.K = p.K;
     a.dq = p.dq; a.dr = p.dr;
@@ -74,9 +74,7 @@ static inline int nvx_rs_fill_args(const nvx_rs_plan &p, int first_input, uint64
     a.qoff = (int)((uint64_t)(pos / (unsigned)p.L) - consumed);
     const int tile_out = NVX_RS_THREADS * p.K;
     a.tiles = (int)((n_out + tile_out - 1) / tile_out);
-    if (chunks > a.tiles) chunks = a.tiles;
-    a.tiles_per_chunk = a.tiles ? (a.tiles + chunks - 1) / chunks : 1;
-    chunks = a.tiles ? (a.tiles + a.tiles_per_chunk - 1) / a.tiles_per_chunk : 1;
+    chunks = nvx_stream_chunks(a.tiles, chunks, 1, &a.tiles_per_chunk);
     // the steps the kernel advances its positions by, as (div L, mod L)
     const uint64_t uL = (uint64_t)p.L, tile_pos = (uint64_t)tile_out * p.M, chunk_pos = tile_pos * (uint64_t)a.tiles_per_chunk;
     a.tile_dq = (uint32_t)(tile_pos / uL); a.tile_dr = (uint32_t)(tile_pos % uL);
@@ -90,8 +88,8 @@ static inline int nvx_rs_fill_args(const nvx_rs_plan &p, int first_input, uint64
 // --------------------------------------------------------------------------------------------------------------- plans
 static inline void nvx_rs_plan_release(nvx_rs_plan &p)
 {
-    (void)hipFree(p.d_taps); (void)hipFree(p.d_hist[0]); (void)hipFree(p.d_hist[1]);
-    (void)hipFree(p.d_push_in); (void)hipFree(p.d_push_out);
+    (void)hipFree(p.d_taps);
+    p.hist.release(); p.push.release();
     p.timer.destroy();
 }
 
@@ -109,7 +107,6 @@ static inline int nvx_rs_plan_create(nvx_rs_plan &p, const char *what, int devic
     p.device = device; p.n_inputs = n_inputs; p.format = format; p.rate = rate;
     if (!nvx_rs_plan_shape(p, L, M, T)) { set_error("%s: %u S/s: one tile's input does not fit the kernel's staging area", what, rate); return NVX_ERR_ARG; }
     p.consumed.assign(n_inputs, 0);
-    p.parity.assign(n_inputs, 0);
 
     // the table the kernel reads: copy `shift` of phase r holds h[r][T-1-i] at position shift + i
     std::vector<uint16_t> table((size_t)p.tap_dw * 2, 0);
@@ -117,14 +114,12 @@ static inline int nvx_rs_plan_create(nvx_rs_plan &p, const char *what, int devic
         for (int ph = 0; ph < L; ph++)
             for (int i = 0; i < T; i++)
                 table[((size_t)(sh * L + ph) * p.row_dw) * 2 + sh + i] = (uint16_t)taps[(size_t)ph * T + (T - 1 - i)];
-    const size_t hist_bytes = (size_t)n_inputs * p.hist_pitch * 4;
     hipError_t e = hipMalloc((void **)&p.d_taps, (size_t)p.tap_dw * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&p.d_hist[0], hist_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&p.d_hist[1], hist_bytes);
+    if (e == hipSuccess) e = p.hist.allocate(n_inputs, p.hist.words);
     if (e != hipSuccess) { set_error("%s: allocation failed: %s", what, hipGetErrorString(e)); return NVX_ERR_NOMEM; }
     e = hipMemcpy(p.d_taps, table.data(), (size_t)p.tap_dw * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(p.d_hist[0], 0, hist_bytes);
-    if (e == hipSuccess) e = hipMemset(p.d_hist[1], 0, hist_bytes);
+    if (e == hipSuccess) e = hipMemset(p.hist.d[0], 0, p.hist.bytes(n_inputs));
+    if (e == hipSuccess) e = hipMemset(p.hist.d[1], 0, p.hist.bytes(n_inputs));
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { set_error("%s: filling the tables failed: %s", what, hipGetErrorString(e)); return NVX_ERR_HIP; }
     return NVX_OK;
@@ -132,7 +127,7 @@ static inline int nvx_rs_plan_create(nvx_rs_plan &p, const char *what, int devic
 
 static inline int nvx_rs_reset(nvx_rs_plan &p, const char *what, int input)
 {
-    if (input < -1 || input >= p.n_inputs) { set_error("%s: %s %d of %d", what, p.noun, input, p.n_inputs); return NVX_ERR_ARG; }
+    if (!row_ok(what, p.noun, input, -1, p.n_inputs)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(p.mu);
     // a row at position 0 has silence in front: its history rows are not read before they are written again
     for (int i = input < 0 ? 0 : input; i < (input < 0 ? p.n_inputs : input + 1); i++) p.consumed[i] = 0;
@@ -141,24 +136,11 @@ static inline int nvx_rs_reset(nvx_rs_plan &p, const char *what, int input)
 
 static inline int nvx_rs_position(nvx_rs_plan &p, const char *what, int input, uint64_t *consumed, uint64_t *produced)
 {
-    if (input < 0 || input >= p.n_inputs) { set_error("%s: %s %d of %d", what, p.noun, input, p.n_inputs); return NVX_ERR_ARG; }
+    if (!row_ok(what, p.noun, input, 0, p.n_inputs)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(p.mu);
     if (consumed) *consumed = p.consumed[input];
     if (produced) *produced = nvx_rs_outputs_after(p.consumed[input], p.L, p.M);
     return NVX_OK;
-}
-
-static inline int nvx_rs_timing(nvx_rs_plan &p, int enable)
-{
-    std::lock_guard<std::mutex> lk(p.mu);
-    p.timer.enabled = enable != 0;
-    return NVX_OK;
-}
-
-static inline int nvx_rs_time_stats(nvx_rs_plan &p, double *sum_ms, uint64_t *launches, int reset)
-{
-    std::lock_guard<std::mutex> lk(p.mu);
-    return p.timer.collect(sum_ms, launches, reset);
 }
 
 // --------------------------------------------------------------------------------------------------------------- calls
@@ -173,7 +155,7 @@ struct nvx_rs_call {
 // the position's bound and the output count, for a call of n_in samples from `consumed`
 static inline int nvx_rs_call_count(const nvx_rs_plan &p, const char *what, uint64_t consumed, size_t n_in, nvx_rs_call *c)
 {
-    if ((consumed + n_in) >> 62) { set_error("%s: the position passes 2^62", what); return NVX_ERR_ARG; }
+    if (!position_ok(what, consumed + n_in)) return NVX_ERR_ARG;
     c->consumed = consumed;
     c->outs = (size_t)(nvx_rs_outputs_after(consumed + n_in, p.L, p.M) - nvx_rs_outputs_after(consumed, p.L, p.M));
     return NVX_OK;
@@ -187,13 +169,8 @@ static inline int nvx_rs_resident_open(const nvx_rs_plan &p, const char *what, c
         set_error("%s: bad argument (null pointer, input not 16-byte aligned, output not 4-byte aligned, or more than 2^30 samples)", what);
         return NVX_ERR_ARG;
     }
-    for (int i = 1; i < p.n_inputs; i++)
-        if (p.consumed[i] != p.consumed[0]) {
-            set_error("%s: %s %d stands at %llu, %s 0 at %llu: all %ss of a call stand at the same position", what, p.noun, i,
-                      (unsigned long long)p.consumed[i], p.noun, (unsigned long long)p.consumed[0], p.noun);
-            return NVX_ERR_STATE;
-        }
-    c->parity = p.parity[0];
+    if (!all_stand_together(what, p.noun, p.consumed)) return NVX_ERR_STATE;
+    c->parity = p.hist.parity[0];
     return nvx_rs_call_count(p, what, p.consumed[0], n_in, c);
 }
 
@@ -223,19 +200,14 @@ static inline int nvx_rs_resident_ready(nvx_rs_plan &p, const char *what, size_t
     if ((rc = select_device(p.device, p.library)) != NVX_OK) return rc;
     if ((rc = check_device_span(d_in, c.in_bytes, what, "input")) != NVX_OK) return rc;
     if ((rc = check_device_span(d_out, c.out_bytes, what, "output")) != NVX_OK) return rc;
-    for (int i = 1; i < p.n_inputs; i++)
-        if (p.parity[i] != c.parity) {
-            HIP_TRY(hipMemcpyAsync(p.d_hist[c.parity] + (size_t)i * p.hist_pitch, p.d_hist[c.parity ^ 1] + (size_t)i * p.hist_pitch,
-                                   (size_t)p.hist_pitch * 4, hipMemcpyDeviceToDevice, s));
-            p.parity[i] = (uint8_t)c.parity;
-        }
-    return NVX_OK;
+    return p.hist.align(nullptr, s);
 }
 
 // behind a launch over input rows [first_input, first_input + n): they have consumed n_in more and read the other row next
 static inline void nvx_rs_advance(nvx_rs_plan &p, int first_input, int n, size_t n_in, const nvx_rs_call &c)
 {
-    for (int i = first_input; i < first_input + n; i++) { p.consumed[i] = c.consumed + n_in; p.parity[i] = (uint8_t)(c.parity ^ 1); }
+    for (int i = first_input; i < first_input + n; i++) p.consumed[i] = c.consumed + n_in;
+    p.hist.flip(first_input, n, c.parity);
 }
 
 // A push, first step: the arguments and the count.  Whether the caller's buffer holds the outputs is the caller's check.
@@ -246,7 +218,7 @@ static inline int nvx_rs_push_open(const nvx_rs_plan &p, const char *what, int i
         set_error("%s: bad argument (%s %d of %d, null pointer, or more than 2^30 samples)", what, p.noun, input, p.n_inputs);
         return NVX_ERR_ARG;
     }
-    c->parity = p.parity[input];
+    c->parity = p.hist.parity[input];
     return nvx_rs_call_count(p, what, p.consumed[input], n_in, c);
 }
 
@@ -256,17 +228,8 @@ static inline int nvx_rs_push_stage(nvx_rs_plan &p, const char *what, const void
     int rc;
     if ((rc = select_device(p.device, p.library)) != NVX_OK) return rc;
     const size_t in_bytes = n_in * (size_t)NVX_RS_BPS[p.format];
-    if (in_bytes > p.push_in_cap) {
-        (void)hipFree(p.d_push_in); p.d_push_in = nullptr; p.push_in_cap = 0;
-        if (hipMalloc(&p.d_push_in, in_bytes) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, in_bytes); return NVX_ERR_NOMEM; }
-        p.push_in_cap = in_bytes;
-    }
-    if (out_words > p.push_out_cap) {
-        (void)hipFree(p.d_push_out); p.d_push_out = nullptr; p.push_out_cap = 0;
-        if (hipMalloc((void **)&p.d_push_out, out_words * 4) != hipSuccess) { set_error("%s: hipMalloc of %zu bytes failed", what, out_words * 4); return NVX_ERR_NOMEM; }
-        p.push_out_cap = out_words;
-    }
-    HIP_TRY(hipMemcpy(p.d_push_in, in, in_bytes, hipMemcpyHostToDevice));
+    if ((rc = p.push.reserve(what, in_bytes, out_words)) != NVX_OK) return rc;
+    HIP_TRY(hipMemcpy(p.push.d_in, in, in_bytes, hipMemcpyHostToDevice));
     return NVX_OK;
 }
 

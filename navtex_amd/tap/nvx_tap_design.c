@@ -1,34 +1,11 @@
 /* nvx_tap_design.c -- the channel tap's plan on the host (include/navtex_amd_tap.h): L, M, T from the rate and kind, the
  * int32 taps of the Kaiser-windowed sinc at S = 21, and the grid rules of shift and pitch.  Plain C, no device.  The Kaiser,
- * sinc and rounding code is the resampler's (navtex_amd/resample/nvx_resample_design.c), copied as the narrowband
- * interpolator copies it: the libraries share no object. */
-#include <math.h>
-#include <stdlib.h>
-
+ * sinc and rounding code is csrc/nvx_polyphase_design.h's, which the resampler and the narrowband interpolator compile too;
+ * here are the ranges, the band edges, the bounds on a phase's sums and the two grids. */
 #include "nvx_tap_plan.h"
 
 #define PASS_HZ 25000.0                      /* nvx_set_carrier's range */
 #define PASS_FRACTION 0.4                    /* of fo, where that is less: the interpolator's band */
-#define DESIGN_DB 90.0
-
-static uint64_t gcd_u64(uint64_t a, uint64_t b)
-{
-    while (b) { uint64_t t = a % b; a = b; b = t; }
-    return a;
-}
-
-/* modified Bessel function I0 by its power series */
-static double bessel_i0(double x)
-{
-    double sum = 1.0, term = 1.0;
-    const double h = 0.5 * x;
-    for (int k = 1; k < 200; k++) {
-        term *= (h / k) * (h / k);
-        sum += term;
-        if (term < 1e-17 * sum) break;
-    }
-    return sum;
-}
 
 static int rate_ok(uint32_t fo, int kind, const char **why)
 {
@@ -51,19 +28,15 @@ static void edges(uint32_t fo, int kind, double *fp, double *fs)
 int nvx_tap_plan_numbers(uint32_t fo, int kind, int *L, int *M, int *T, const char **why)
 {
     if (!rate_ok(fo, kind, why)) return NVX_ERR_ARG;
-    const uint64_t g = gcd_u64(NVX_TAP_INPUT_RATE, fo);
+    const uint64_t g = nvx_pp_gcd(NVX_TAP_INPUT_RATE, fo);
     const uint64_t l = fo / g, m = NVX_TAP_INPUT_RATE / g;
-    /* Kaiser's estimate of the prototype's length at rate L * 252000 for the transition from fp to fs */
+    /* the prototype runs at rate L * 252000; the transition is from fp to fs */
     double fp, fs;
     edges(fo, kind, &fp, &fs);
     const double rate = (double)l * NVX_TAP_INPUT_RATE;
-    const double dw = 2.0 * M_PI * (fs - fp) / rate;
-    const double order = (DESIGN_DB - 7.95) / (2.285 * dw);
-    const double per_phase = ceil((order + 1.0) / (double)l);
+    const double per_phase = nvx_pp_kaiser_per_phase(fs - fp, rate, (double)l);
     if (per_phase * (double)l > 2.0 * NVX_TAP_MAX_TAPS) { *why = "the rate needs more than 32768 taps (L * T, L / M = rate / 252000 in lowest terms)"; return NVX_ERR_ARG; }
-    int t = (int)per_phase;
-    if (t & 1) t++;
-    if (t < 8) t = 8;
+    const int t = nvx_pp_even_taps(per_phase);
     if ((long)l * t > NVX_TAP_MAX_TAPS) { *why = "the rate needs more than 32768 taps (L * T, L / M = rate / 252000 in lowest terms)"; return NVX_ERR_ARG; }
     *L = (int)l; *M = (int)m; *T = t;
     return NVX_OK;
@@ -71,36 +44,21 @@ int nvx_tap_plan_numbers(uint32_t fo, int kind, int *L, int *M, int *T, const ch
 
 int nvx_tap_plan_taps(uint32_t fo, int kind, int L, int T, int32_t *taps, const char **why)
 {
-    const int nt = L * T;
-    double *p = (double *)malloc((size_t)nt * sizeof(double));
-    if (!p) { *why = "out of memory"; return NVX_ERR_NOMEM; }
     double fp, fs;
     edges(fo, kind, &fp, &fs);
     const double fc = 0.5 * (fp + fs) / ((double)L * NVX_TAP_INPUT_RATE);      /* the middle of the transition, in cycles per sample of the prototype */
-    const double beta = 0.1102 * (DESIGN_DB - 8.7);
-    const double centre = 0.5 * (nt - 1), i0b = bessel_i0(beta);
-    for (int k = 0; k < nt; k++) {
-        const double d = k - centre, u = d / (centre + 0.5);     /* the window reaches zero half a sample beyond the ends */
-        const double a = 2.0 * M_PI * fc * d;
-        const double sinc = fabs(a) < 1e-12 ? 1.0 : sin(a) / a;
-        p[k] = 2.0 * fc * sinc * bessel_i0(beta * sqrt(1.0 - u * u)) / i0b;
-    }
+    long long *row;
+    double *p = nvx_pp_prototype(fc, L, T, &row);
+    if (!p) { *why = "out of memory"; return NVX_ERR_NOMEM; }
     int rc = NVX_OK;
     for (int r = 0; r < L && rc == NVX_OK; r++) {
-        double sum = 0.0;
-        for (int t = 0; t < T; t++) sum += p[r + t * L];
-        long long isum = 0, asum = 0, hsum = 0;
-        int big = 0;
-        for (int t = 0; t < T; t++) {
-            const long long v = llrint(p[r + t * L] / sum * (double)(1 << NVX_TAP_SHIFT));
-            taps[r * T + t] = (int32_t)v;                        /* |v| <= about 2^21: a phase is at most a unit pulse */
-            isum += v;
-            if (llabs(v) > llabs((long long)taps[r * T + big])) big = t;
-        }
+        int big;
+        const long long isum = nvx_pp_phase(p, L, T, r, NVX_TAP_SHIFT, row, &big);
+        long long asum = 0, hsum = 0;
         /* the rounding residue onto the largest tap */
-        taps[r * T + big] = (int32_t)((long long)taps[r * T + big] + ((1LL << NVX_TAP_SHIFT) - isum));
+        row[big] += (1LL << NVX_TAP_SHIFT) - isum;
         for (int t = 0; t < T; t++) {
-            const long long v = taps[r * T + t], hh = v >> 8;    /* arithmetic: v = 256 hh + hl, hl in [0, 255] */
+            const long long v = taps[r * T + t] = (int32_t)row[t], hh = v >> 8;     /* |v| <= about 2^21; arithmetic: v = 256 hh + hl, hl in [0, 255] */
             asum += llabs(v); hsum += llabs(hh);
         }
         if (hsum > 65535) { *why = "a phase's Sum |h >> 8| exceeds 65535: the high half's sum could leave int32"; rc = NVX_ERR_ARG; }

@@ -1,7 +1,7 @@
 // nvx_tap_host.cpp -- the channel tap's entry points (include/navtex_amd_tap.h): the design, grid and table without a device,
-// the config checks, the plan with its tap table, shifts, pitches, carried positions and state rows, the checks of a call,
-// and a push's staging.  The launch arithmetic is nvx_tap_plan.h's.  The library stands alone: it shares no state with any
-// other.
+// the config checks, the plan with its tap table, shifts, pitches and carried positions, and the checks of a call.  The state
+// rows, a push's staging, the row and position checks and the timing bodies are nvx_companion.h's, the launch arithmetic
+// nvx_tap_plan.h's.  The library stands alone: it shares no state with any other.
 #include <cstring>
 #include <mutex>
 #include <new>
@@ -26,16 +26,14 @@ struct nvx_tap {
     nvx_tap_args shape = {};                                // L, M, T and what follows from them
     int16_t *d_table = nullptr;
     uint32_t *d_w = nullptr;
-    uint32_t *d_state[2] = { nullptr, nullptr };            // [n_inputs][state_pitch], read and written alternately
+    nvx_state_rows<uint32_t> state;                         // [n_inputs][T]
     int *d_kk = nullptr, *h_kk = nullptr;                   // [2][rows]: shifts, then pitches; the pinned row they are uploaded from
     std::vector<int> kk;
     bool kk_dirty = true;
     hipEvent_t kk_uploaded = nullptr;
     std::vector<uint64_t> consumed;
-    std::vector<uint8_t> parity;                            // which state row the input's next launch reads
     nvx_event_timer timer;
-    uint32_t *d_push_in = nullptr; void *d_push_out = nullptr;
-    size_t push_in_cap = 0, push_out_cap = 0;               // words, bytes
+    nvx_push_staging push;                                  // 4-byte input words; the output in words too, rounded up (audio is int16)
     struct { int tile_out, tiles, form, waves; size_t lds_bytes; } last = {};
     int64_t kernel_launches = 0;
 
@@ -49,13 +47,7 @@ static bool valid(const nvx_tap *c, const char *what)
     return true;
 }
 
-static bool input_ok(const nvx_tap *c, const char *what, int input, int lowest)
-{
-    if (input < lowest || input >= c->n_inputs) { set_error("%s: input %d of %d", what, input, c->n_inputs); return false; }
-    return true;
-}
-
-static bool row_ok(const nvx_tap *c, const char *what, int input, int lowest, int tap)
+static bool input_tap_ok(const nvx_tap *c, const char *what, int input, int lowest, int tap)
 {
     if (input < lowest || input >= c->n_inputs || tap < 0 || tap >= c->n_taps) {
         set_error("%s: input %d of %d, tap %d of %d", what, input, c->n_inputs, tap, c->n_taps);
@@ -109,8 +101,8 @@ extern "C" void nvx_tap_config_default(nvx_tap_config *cfg)
 // --------------------------------------------------------------------------------------------------------------- plans
 static void release(nvx_tap *c)
 {
-    (void)hipFree(c->d_table); (void)hipFree(c->d_w); (void)hipFree(c->d_state[0]); (void)hipFree(c->d_state[1]); (void)hipFree(c->d_kk);
-    (void)hipHostFree(c->h_kk); (void)hipFree(c->d_push_in); (void)hipFree(c->d_push_out);
+    (void)hipFree(c->d_table); (void)hipFree(c->d_w); (void)hipFree(c->d_kk); (void)hipHostFree(c->h_kk);
+    c->state.release(); c->push.release();
     if (c->kk_uploaded) (void)hipEventDestroy(c->kk_uploaded);
     c->timer.destroy();
     c->magic = 0;
@@ -149,7 +141,7 @@ extern "C" int nvx_tap_create(const nvx_tap_config *cfg, nvx_tap **out)
     c->device = cfg->device; c->n_inputs = cfg->n_inputs; c->n_taps = cfg->n_taps; c->kind = cfg->kind; c->fo = cfg->output_rate_hz;
     nvx_tap_fill_shape(L, M, T, &c->shape);
     c->shape.state_pitch = T; c->shape.n_taps = cfg->n_taps;
-    c->consumed.assign(cfg->n_inputs, 0); c->parity.assign(cfg->n_inputs, 0);
+    c->consumed.assign(cfg->n_inputs, 0);
     const size_t rows = c->rows();
     c->kk.assign(2 * rows, 0);
     for (size_t i = 0; i < rows; i++) c->kk[rows + i] = kp;
@@ -175,16 +167,15 @@ extern "C" int nvx_tap_create(const nvx_tap_config *cfg, nvx_tap **out)
     const size_t table_bytes = table.size() * sizeof(int16_t), state_bytes = (size_t)cfg->n_inputs * T * sizeof(uint32_t);
     hipError_t e = hipMalloc((void **)&c->d_table, table_bytes);
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_w, w.size() * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_state[0], state_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **)&c->d_state[1], state_bytes);
+    if (e == hipSuccess) e = c->state.allocate(cfg->n_inputs, (size_t)T);
     if (e == hipSuccess) e = hipMalloc((void **)&c->d_kk, 2 * rows * sizeof(int));
     if (e == hipSuccess) e = hipHostMalloc((void **)&c->h_kk, 2 * rows * sizeof(int), hipHostMallocDefault);
     if (e != hipSuccess) { set_error("%s: allocation failed: %s", what, hipGetErrorString(e)); release(c); return NVX_ERR_NOMEM; }
     e = hipEventCreateWithFlags(&c->kk_uploaded, hipEventDisableTiming);
     if (e == hipSuccess) e = hipMemcpy(c->d_table, table.data(), table_bytes, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(c->d_w, w.data(), w.size() * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(c->d_state[0], 0, state_bytes);
-    if (e == hipSuccess) e = hipMemset(c->d_state[1], 0, state_bytes);
+    if (e == hipSuccess) e = hipMemset(c->state.d[0], 0, state_bytes);
+    if (e == hipSuccess) e = hipMemset(c->state.d[1], 0, state_bytes);
     if (e == hipSuccess) e = hipMemset(c->d_kk, 0, 2 * rows * sizeof(int));
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { set_error("%s: filling the tables and the state failed: %s", what, hipGetErrorString(e)); release(c); return NVX_ERR_HIP; }
@@ -217,7 +208,7 @@ extern "C" int nvx_tap_plan(nvx_tap *c, int *L, int *M, int *T, int *n_inputs, i
 extern "C" int nvx_tap_set_shift(nvx_tap *c, int input, int tap, double hz, double *applied_hz)
 {
     const char *what = "nvx_tap_set_shift";
-    if (!valid(c, what) || !row_ok(c, what, input, -1, tap)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !input_tap_ok(c, what, input, -1, tap)) return NVX_ERR_ARG;
     int k;
     const char *why = "";
     if (nvx_tap_shift_k(c->fo, c->kind, hz, &k, &why) != NVX_OK) { set_error("%s: %g Hz at %u S/s: %s", what, hz, c->fo, why); return NVX_ERR_ARG; }
@@ -231,7 +222,7 @@ extern "C" int nvx_tap_set_shift(nvx_tap *c, int input, int tap, double hz, doub
 extern "C" int nvx_tap_get_shift(nvx_tap *c, int input, int tap, int *k, double *applied_hz)
 {
     const char *what = "nvx_tap_get_shift";
-    if (!valid(c, what) || !row_ok(c, what, input, 0, tap)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !input_tap_ok(c, what, input, 0, tap)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     const int kk = c->kk[(size_t)input * c->n_taps + tap];
     if (k) *k = kk;
@@ -242,7 +233,7 @@ extern "C" int nvx_tap_get_shift(nvx_tap *c, int input, int tap, int *k, double 
 extern "C" int nvx_tap_set_pitch(nvx_tap *c, int input, int tap, double pitch_hz, double *applied_hz)
 {
     const char *what = "nvx_tap_set_pitch";
-    if (!valid(c, what) || !row_ok(c, what, input, -1, tap)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !input_tap_ok(c, what, input, -1, tap)) return NVX_ERR_ARG;
     if (c->kind != NVX_TAP_REAL) { set_error("%s: the plan's kind is NVX_TAP_IQ: only audio has a pitch", what); return NVX_ERR_ARG; }
     int kp;
     const char *why = "";
@@ -257,7 +248,7 @@ extern "C" int nvx_tap_set_pitch(nvx_tap *c, int input, int tap, double pitch_hz
 extern "C" int nvx_tap_get_pitch(nvx_tap *c, int input, int tap, int *kp, double *applied_hz)
 {
     const char *what = "nvx_tap_get_pitch";
-    if (!valid(c, what) || !row_ok(c, what, input, 0, tap)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !input_tap_ok(c, what, input, 0, tap)) return NVX_ERR_ARG;
     if (c->kind != NVX_TAP_REAL) { set_error("%s: the plan's kind is NVX_TAP_IQ: only audio has a pitch", what); return NVX_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     const int k = c->kk[c->rows() + (size_t)input * c->n_taps + tap];
@@ -270,16 +261,15 @@ extern "C" int nvx_tap_get_pitch(nvx_tap *c, int input, int tap, int *kp, double
 // `input` (-1: all) stands at input sample `position` with silence in front of it
 static int restart(nvx_tap *c, const char *what, int input, uint64_t position)
 {
-    if (!input_ok(c, what, input, -1)) return NVX_ERR_ARG;
+    if (!row_ok(what, "input", input, -1, c->n_inputs)) return NVX_ERR_ARG;
     if (position >> 62) { set_error("%s: position %llu (below 2^62)", what, (unsigned long long)position); return NVX_ERR_ARG; }
     std::lock_guard<std::mutex> lk(c->mu);
     int rc;
     if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
     HIP_TRY(hipDeviceSynchronize());
     const int first = input < 0 ? 0 : input, n = input < 0 ? c->n_inputs : 1;
-    const size_t pitch = (size_t)c->shape.state_pitch, bytes = (size_t)n * pitch * sizeof(uint32_t);
-    HIP_TRY(hipMemset(c->d_state[0] + (size_t)first * pitch, 0, bytes));
-    HIP_TRY(hipMemset(c->d_state[1] + (size_t)first * pitch, 0, bytes));
+    HIP_TRY(hipMemset(c->state.in(first, 0), 0, c->state.bytes(n)));
+    HIP_TRY(hipMemset(c->state.in(first, 1), 0, c->state.bytes(n)));
     HIP_TRY(hipDeviceSynchronize());
     for (int i = first; i < first + n; i++) c->consumed[i] = position;
     return NVX_OK;
@@ -298,7 +288,7 @@ extern "C" int nvx_tap_debug_set_position(nvx_tap *c, int input, uint64_t positi
 extern "C" int nvx_tap_position(nvx_tap *c, int input, uint64_t *consumed, uint64_t *produced)
 {
     const char *what = "nvx_tap_position";
-    if (!valid(c, what) || !input_ok(c, what, input, 0)) return NVX_ERR_ARG;
+    if (!valid(c, what) || !row_ok(what, "input", input, 0, c->n_inputs)) return NVX_ERR_ARG;
     std::lock_guard<std::mutex> lk(c->mu);
     if (consumed) *consumed = c->consumed[input];
     if (produced) *produced = nvx_tap_outputs_after(c->consumed[input], c->shape.L, c->shape.M);
@@ -307,17 +297,12 @@ extern "C" int nvx_tap_position(nvx_tap *c, int input, uint64_t *consumed, uint6
 
 extern "C" int nvx_tap_timing(nvx_tap *c, int enable)
 {
-    if (!valid(c, "nvx_tap_timing")) return NVX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    c->timer.enabled = enable != 0;
-    return NVX_OK;
+    return valid(c, "nvx_tap_timing") ? timing_enable(c->mu, c->timer, enable) : NVX_ERR_ARG;
 }
 
 extern "C" int nvx_tap_time_stats(nvx_tap *c, double *sum_ms, uint64_t *calls, int reset)
 {
-    if (!valid(c, "nvx_tap_time_stats")) return NVX_ERR_ARG;
-    std::lock_guard<std::mutex> lk(c->mu);
-    return c->timer.collect(sum_ms, calls, reset);
+    return valid(c, "nvx_tap_time_stats") ? timing_collect(c->mu, c->timer, sum_ms, calls, reset) : NVX_ERR_ARG;
 }
 
 extern "C" int64_t nvx_tap_debug_last_launch(nvx_tap *c, int *tile_out, int *tiles, int *form, int *waves, size_t *lds_bytes)
@@ -339,7 +324,7 @@ extern "C" int64_t nvx_tap_debug_last_launch(nvx_tap *c, int *tile_out, int *til
 static bool call_outputs(const nvx_tap *c, const char *what, uint64_t consumed, size_t n_in, size_t *outs)
 {
     if (n_in > NVX_TAP_MAX_IN) { set_error("%s: %zu samples (at most 2^30 per call)", what, n_in); return false; }
-    if ((consumed + n_in) >> 62) { set_error("%s: the position passes 2^62", what); return false; }
+    if (!position_ok(what, consumed + n_in)) return false;
     *outs = (size_t)(nvx_tap_outputs_after_wide(consumed + n_in, c->shape.L, c->shape.M) - nvx_tap_outputs_after_wide(consumed, c->shape.L, c->shape.M));
     return true;                                            // L / M < 1: fewer outputs than samples
 }
@@ -363,9 +348,9 @@ static int launch(nvx_tap *c, int first, int n, uint64_t consumed, int parity, c
                   size_t pitch_out, size_t out_first, hipStream_t s)
 {
     nvx_tap_args a = c->shape;
-    const size_t row0 = (size_t)first * c->n_taps, sp = (size_t)a.state_pitch;
+    const size_t row0 = (size_t)first * c->n_taps;
     a.in = d_in; a.pitch_in = pitch_in; a.out = d_out; a.pitch_out = pitch_out; a.out_first = out_first;
-    a.state_in = c->d_state[parity] + (size_t)first * sp; a.state_out = c->d_state[parity ^ 1] + (size_t)first * sp;
+    a.state_in = c->state.in(first, parity); a.state_out = c->state.out(first, parity);
     a.table = c->d_table; a.w = c->d_w; a.k = c->d_kk + row0; a.kp = c->d_kk + c->rows() + row0;
     nvx_tap_fill_args(consumed, n_in, &a);
     int rc;
@@ -376,7 +361,8 @@ static int launch(nvx_tap *c, int first, int n, uint64_t consumed, int parity, c
     c->last = { a.tile_out, a.tiles, a.uniform ? 1 : 2, a.tile_out >> 6, nvx_tap_lds_bytes(&a) };
     c->kernel_launches += 1;
     if ((rc = c->timer.end(s, ev)) != NVX_OK) return rc;
-    for (int i = first; i < first + n; i++) { c->consumed[i] = consumed + n_in; c->parity[i] = (uint8_t)(parity ^ 1); }
+    for (int i = first; i < first + n; i++) c->consumed[i] = consumed + n_in;
+    c->state.flip(first, n, parity);
     return NVX_OK;
 }
 
@@ -391,12 +377,7 @@ extern "C" int nvx_tap_resident(nvx_tap *c, const void *d_in, size_t pitch_in, s
         set_error("%s: bad argument (null pointer, input not 4-byte aligned, or output not aligned to its sample)", what);
         return NVX_ERR_ARG;
     }
-    for (int i = 1; i < c->n_inputs; i++)
-        if (c->consumed[i] != c->consumed[0]) {
-            set_error("%s: input %d stands at %llu, input 0 at %llu: all inputs of a call stand at the same position", what, i,
-                      (unsigned long long)c->consumed[i], (unsigned long long)c->consumed[0]);
-            return NVX_ERR_STATE;
-        }
+    if (!all_stand_together(what, "input", c->consumed)) return NVX_ERR_STATE;
     const uint64_t consumed = c->consumed[0];
     size_t outs;
     if (!call_outputs(c, what, consumed, n_in, &outs)) return NVX_ERR_ARG;
@@ -421,15 +402,8 @@ extern "C" int nvx_tap_resident(nvx_tap *c, const void *d_in, size_t pitch_in, s
     if (outs && (rc = check_device_span(d_out, out_bytes, what, "output")) != NVX_OK) return rc;
     hipStream_t s = (hipStream_t)hip_stream;
     // the state rows of inputs pushed one by one are brought to input 0's parity
-    const int parity = c->parity[0];
-    const size_t sp = (size_t)c->shape.state_pitch;
-    for (int i = 1; i < c->n_inputs; i++)
-        if (c->parity[i] != parity) {
-            HIP_TRY(hipMemcpyAsync(c->d_state[parity] + (size_t)i * sp, c->d_state[parity ^ 1] + (size_t)i * sp, sp * sizeof(uint32_t),
-                                   hipMemcpyDeviceToDevice, s));
-            c->parity[i] = (uint8_t)parity;
-        }
-    return launch(c, 0, c->n_inputs, consumed, parity, (const uint32_t *)d_in, pitch_in, n_in, d_out, pitch_out, out_first, s);
+    if ((rc = c->state.align(nullptr, s)) != NVX_OK) return rc;
+    return launch(c, 0, c->n_inputs, consumed, c->state.parity[0], (const uint32_t *)d_in, pitch_in, n_in, d_out, pitch_out, out_first, s);
 }
 
 extern "C" int nvx_tap_push(nvx_tap *c, int input, const void *in, size_t n_in, int16_t *out, size_t cap_samples, size_t *n_out)
@@ -451,20 +425,11 @@ extern "C" int nvx_tap_push(nvx_tap *c, int input, const void *in, size_t n_in, 
     if (n_in == 0) return NVX_OK;
     int rc;
     if ((rc = select_device(c->device, NOUN)) != NVX_OK) return rc;
-    if (n_in > c->push_in_cap) {
-        (void)hipFree(c->d_push_in); c->d_push_in = nullptr; c->push_in_cap = 0;
-        if (hipMalloc((void **)&c->d_push_in, n_in * 4) != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of %zu bytes failed", what, n_in * 4); return NVX_ERR_NOMEM; }
-        c->push_in_cap = n_in;
-    }
     const size_t pitch = outs ? outs : 1, out_bytes = (size_t)c->n_taps * pitch * osize;
-    if (out_bytes > c->push_out_cap) {
-        (void)hipFree(c->d_push_out); c->d_push_out = nullptr; c->push_out_cap = 0;
-        if (hipMalloc(&c->d_push_out, out_bytes) != hipSuccess) { (void)hipGetLastError(); set_error("%s: hipMalloc of %zu bytes failed", what, out_bytes); return NVX_ERR_NOMEM; }
-        c->push_out_cap = out_bytes;
-    }
-    HIP_TRY(hipMemcpy(c->d_push_in, in, n_in * 4, hipMemcpyHostToDevice));
-    if ((rc = launch(c, input, 1, consumed, c->parity[input], c->d_push_in, n_in, n_in, c->d_push_out, pitch, 0, nullptr)) != NVX_OK) return rc;
-    if (outs) HIP_TRY(hipMemcpy2D(out, cap_samples * osize, c->d_push_out, pitch * osize, outs * osize, (size_t)c->n_taps, hipMemcpyDeviceToHost));
+    if ((rc = c->push.reserve(what, n_in * 4, (out_bytes + 3) / 4)) != NVX_OK) return rc;
+    HIP_TRY(hipMemcpy(c->push.d_in, in, n_in * 4, hipMemcpyHostToDevice));
+    if ((rc = launch(c, input, 1, consumed, c->state.parity[input], (const uint32_t *)c->push.d_in, n_in, n_in, c->push.d_out, pitch, 0, nullptr)) != NVX_OK) return rc;
+    if (outs) HIP_TRY(hipMemcpy2D(out, cap_samples * osize, c->push.d_out, pitch * osize, outs * osize, (size_t)c->n_taps, hipMemcpyDeviceToHost));
     else HIP_TRY(hipStreamSynchronize(nullptr));
     return NVX_OK;
 }

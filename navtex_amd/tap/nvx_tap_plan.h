@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "navtex_amd_tap.h"
+#include "nvx_polyphase_design.h"
 
 #define NVX_TAP_THREADS 256                 /* a workgroup's threads at most: one output each */
 #define NVX_TAP_LDS_BUDGET (80 * 1024)      /* a workgroup takes a tile of 256 outputs, or of 128 where 256 do not stage within this */
@@ -27,11 +28,8 @@ int nvx_tap_shift_k(uint32_t fo, int kind, double hz, int *k, const char **why);
 int nvx_tap_pitch_k(uint32_t fo, double pitch_hz, int *kp, const char **why);
 
 /* ceil(n * L / M) for n < 2^63, in full and as its low 64 bits */
-static inline unsigned __int128 nvx_tap_outputs_after_wide(uint64_t n, int L, int M)
-{
-    return ((unsigned __int128)n * (unsigned)L + (unsigned)(M - 1)) / (unsigned)M;
-}
-static inline uint64_t nvx_tap_outputs_after(uint64_t n, int L, int M) { return (uint64_t)nvx_tap_outputs_after_wide(n, L, M); }
+static inline unsigned __int128 nvx_tap_outputs_after_wide(uint64_t n, int L, int M) { return nvx_pp_outputs_after_wide(n, L, M); }
+static inline uint64_t nvx_tap_outputs_after(uint64_t n, int L, int M) { return nvx_pp_outputs_after(n, L, M); }
 
 /* For tests: the shape of the plan's last call -- the outputs of a tile (the workgroup's threads), the tiles of a row, the
  * form (1: taps wave-uniform through the scalar cache; 2: taps per lane through the vector cache), the waves of a

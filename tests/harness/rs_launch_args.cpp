@@ -3,6 +3,7 @@
 // 128-bit integers.  The kernels' walk over chunks, tiles and threads is restated here step by step -- the two
 // shift-and-subtract divisions as plain divisions with the bounds they rely on asserted -- and every output of the call must
 // be reached exactly once, at input position (n0 + j) M div L - consumed and phase (n0 + j) M mod L, n0 = ceil(consumed L / M).
+// The chunk split is nvx_stream_plan.h's with a shortest chunk of one tile: it is held against the plan's rule restated here.
 // Built with -fsanitize=address,undefined by tests/test_resample.py; links the design (nvx_resample_design.c), no HIP.
 #include <cstdio>
 #include <cstdlib>
@@ -35,6 +36,35 @@ static void check_step(const where &w, const char *name, u128 steps, const nvx_r
     CHECK((u128)q * (unsigned)p.L + r == pos && r < (uint32_t)p.L, AT ": step %s = (%u, %u)", ATV(w), name, q, r);
 }
 
+// The chunk split of the plan restated: at most a chunk per tile, equal shares, for no tiles one chunk of one tile.
+// nvx_rs_fill_args gets it from nvx_stream_chunks(tiles, chunks, 1, ...).
+static int split_in_equal_shares(int tiles, int chunks, int *tiles_per_chunk)
+{
+    if (chunks > tiles) chunks = tiles;
+    *tiles_per_chunk = tiles ? (tiles + chunks - 1) / chunks : 1;
+    return tiles ? (tiles + *tiles_per_chunk - 1) / *tiles_per_chunk : 1;
+}
+
+// nvx_stream_chunks with a shortest chunk of one tile is that split, for every chunks >= 1
+static void check_split(void)
+{
+    static const int WANTED[] = { 1, 2, 3, 4, 5, 7, 8, 15, 16, 17, 31, 64, 100, 255, 256, 257, 683, 1024, 2047, 2048, 2049, 65535, 1 << 20 };
+    for (int tiles = 0; tiles <= 3000; tiles++)
+        for (int wanted : WANTED) {
+            int per_old, per_new;
+            const int old_chunks = split_in_equal_shares(tiles, wanted, &per_old), new_chunks = nvx_stream_chunks(tiles, wanted, 1, &per_new);
+            CHECK(old_chunks == new_chunks && per_old == per_new, "%d tiles, %d wanted: %d chunks of %d, nvx_stream_chunks %d of %d", tiles, wanted, old_chunks,
+                  per_old, new_chunks, per_new);
+        }
+    for (int tiles = 0; tiles <= 300; tiles++)
+        for (int wanted = 1; wanted <= 320; wanted++) {
+            int per_old, per_new;
+            const int old_chunks = split_in_equal_shares(tiles, wanted, &per_old), new_chunks = nvx_stream_chunks(tiles, wanted, 1, &per_new);
+            CHECK(old_chunks == new_chunks && per_old == per_new, "%d tiles, %d wanted: %d chunks of %d, nvx_stream_chunks %d of %d", tiles, wanted, old_chunks,
+                  per_old, new_chunks, per_new);
+        }
+}
+
 static void check_case(const nvx_rs_plan &p, const where &w, uint64_t consumed, size_t n_in)
 {
     const uint32_t L = (uint32_t)p.L;
@@ -45,8 +75,8 @@ static void check_case(const nvx_rs_plan &p, const where &w, uint64_t consumed, 
 
     // what is handed through
     CHECK(a.in == out.data() && a.out == out.data() && a.pitch_in == 12345 && a.pitch_out == 6789 && a.out_first == 77, AT ": operands", ATV(w));
-    CHECK(a.hist_in == p.d_hist[1] + p.hist_pitch && a.hist_out == p.d_hist[0] + p.hist_pitch && a.taps == p.d_taps, AT ": history rows", ATV(w));
-    CHECK(a.hist_pitch == p.hist_pitch && a.hist_valid == (consumed > 0) && (size_t)a.n_in == n_in && (size_t)a.n_out == n_out, AT ": counts", ATV(w));
+    CHECK(a.hist_in == p.hist.d[1] + p.hist.words && a.hist_out == p.hist.d[0] + p.hist.words && a.taps == p.d_taps, AT ": history rows", ATV(w));
+    CHECK((size_t)a.hist_pitch == p.hist.words && a.hist_valid == (consumed > 0) && (size_t)a.n_in == n_in && (size_t)a.n_out == n_out, AT ": counts", ATV(w));
     CHECK(a.L == p.L && a.M == p.M && a.T == p.T && a.Tp == p.Tp && a.row_dw == p.row_dw && a.tap_dw == p.tap_dw && a.K == p.K, AT ": plan", ATV(w));
 
     // tiles and chunks: every tile in exactly one chunk, no chunk empty, no more chunks than wanted
@@ -56,6 +86,8 @@ static void check_case(const nvx_rs_plan &p, const where &w, uint64_t consumed, 
     CHECK((long)chunks * a.tiles_per_chunk >= a.tiles && (long)(chunks - 1) * a.tiles_per_chunk < a.tiles, AT ": %d chunks of %d tiles", ATV(w), chunks, a.tiles_per_chunk);
     if (w.wanted == 1) CHECK(chunks == 1 && a.tiles_per_chunk == a.tiles, AT ": one chunk", ATV(w));
     if (w.wanted >= a.tiles) CHECK(chunks == a.tiles && a.tiles_per_chunk == 1, AT ": a chunk per tile", ATV(w));
+    int per;
+    CHECK(chunks == split_in_equal_shares(a.tiles, w.wanted, &per) && a.tiles_per_chunk == per, AT ": %d chunks of %d tiles", ATV(w), chunks, a.tiles_per_chunk);
 
     // the steps, as (div L, mod L)
     check_step(w, "thread (m)", 1, p, a.m_div, a.m_mod);
@@ -120,6 +152,7 @@ static void check_case(const nvx_rs_plan &p, const where &w, uint64_t consumed, 
 
 int main(void)
 {
+    check_split();
     // taps in the LDS; L = 1008, taps in global memory; L = M = 1; the lowest rate (L > M); the largest LDS launch
     static const struct { uint32_t rate; bool taps_in_lds; } PLANS[] = { { 2048000, true }, { 1000250, false }, { 252000, true }, { 96000, true }, { 100100, true } };
     for (const auto &pl : PLANS) {
@@ -132,8 +165,8 @@ int main(void)
         if (pl.rate == 1000250) CHECK(L == 1008, "L %d", L);
         if (pl.rate == 252000) CHECK(L == 1 && M == 1, "L %d M %d", L, M);
         p.n_inputs = 2;
-        std::vector<uint32_t> hist(2 * 2 * (size_t)p.hist_pitch + 1), taps(1);
-        p.d_hist[0] = hist.data(); p.d_hist[1] = hist.data() + 2 * (size_t)p.hist_pitch; p.d_taps = taps.data();
+        std::vector<uint32_t> hist(2 * 2 * p.hist.words + 1), taps(1);
+        p.hist.d[0] = hist.data(); p.hist.d[1] = hist.data() + 2 * p.hist.words; p.d_taps = taps.data();
 
         const size_t tile = (size_t)NVX_RS_THREADS * p.K;
         const size_t n_outs[] = { 1, tile - 1, tile, tile + 1, 5 * tile };

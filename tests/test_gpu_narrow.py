@@ -128,6 +128,33 @@ def test_one_shot_equals_short_calls_push_equals_resident_and_a_reset_stream_rej
         _same(got, [want[0][o2:], fresh.push(other[n1 + n2:]), want[2][o2:]], "rejoined")
 
 
+def test_a_stream_pushed_three_times_meets_two_that_were_not(nv, nb, designs):
+    """3 streams of unsigned bytes (REAL: a byte a sample).  Stream 1 alone is pushed 5, 700 and 3 samples -- the staging grows,
+    then serves a smaller push, and after three launches the stream reads the other of its two state rows -- while streams 0
+    and 2 are set to where it stands with silence in front.  One resident call of a single tile over all three: stream 1's
+    state row is brought over to the others' side first, and every word equals the restatement."""
+    rate, fmt, kind = (12000, 1), nr.U8, nr.REAL
+    L, M, T, h = designs(*rate)
+    pushes, n = (5, 700, 3), 200
+    at = sum(pushes)
+    assert n <= WINDOWS[rate]
+    rows = [nc.signal(fmt, kind, at + n, 700 + s) for s in range(3)]
+    refs = [nr.Interpolator(h, L, M, fmt, kind, position=0 if s == 1 else at) for s in range(3)]
+    with nb.Interpolator(*rate, format=fmt, kind=kind, n_streams=3) as c:
+        pos = 0
+        for cut in pushes:
+            assert np.array_equal(c.push(1, rows[1][pos:pos + cut]), refs[1].push(rows[1][pos:pos + cut])), pos
+            pos += cut
+        launches = c.debug_last_launch()["launches"]
+        assert launches == 3
+        c.debug_set_position(at, stream=0); c.debug_set_position(at, stream=2)
+        assert all(c.position(s) == (at, nr.outputs_after(at, L, M)) for s in range(3))
+        got = _run_resident(nv, c, [row[at:] for row in rows], [n], pitch_extra=1, out_first=1)
+        shape = c.debug_last_launch()
+        assert (shape["launches"], shape["chunks"], shape["tiles_per_chunk"]) == (launches + 1, 1, 1), shape
+        _same(got, [refs[s].push(rows[s][at:]) for s in range(3)], "met")
+
+
 # ------------------------------------------------------------------------------------------------------------------ (c)
 @pytest.mark.parametrize("kind", KINDS, ids=KIND_IDS)
 @pytest.mark.parametrize("fmt", FORMATS, ids=FORMAT_IDS)
