@@ -3,8 +3,8 @@ companions libnavtex_amd_scan.so (the band scan, navtex_amd/scan/), libnavtex_am
 navtex_amd/resample/), libnavtex_amd_ddc.so (the down-converter bank, navtex_amd/ddc/), libnavtex_amd_blank.so (the
 impulse noise blanker, navtex_amd/blank/), libnavtex_amd_iqc.so (the IQ corrector, navtex_amd/iqc/), libnavtex_amd_real.so
 (the real-input converter, navtex_amd/real/), libnavtex_amd_narrow.so (the narrowband interpolator, navtex_amd/narrow/),
-libnavtex_amd_tap.so (the channel tap, navtex_amd/tap/) and libnavtex_amd_anc.so (the antenna noise canceller,
-navtex_amd/anc/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
+libnavtex_amd_tap.so (the channel tap, navtex_amd/tap/), libnavtex_amd_anc.so (the antenna noise canceller,
+navtex_amd/anc/) and libnavtex_amd_notch.so (the tone notch, navtex_amd/notch/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
 reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
@@ -82,6 +82,11 @@ ANC = PKG / "anc"
 ANC_LIB = PKG / "libnavtex_amd_anc.so"
 ANC_HIP_SOURCES = ["nvx_anc.hip"]
 ANC_CXX_SOURCES = ["nvx_anc_host.cpp"]
+# the tone notch (include/navtex_amd_notch.h), built as the canceller is; it also reads the bank's table header nvx_ddc_table.h
+NOTCH = PKG / "notch"
+NOTCH_LIB = PKG / "libnavtex_amd_notch.so"
+NOTCH_HIP_SOURCES = ["nvx_notch.hip"]
+NOTCH_CXX_SOURCES = ["nvx_notch_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp", "nvx_afc.cpp"]
 # automatic frequency control (include/navtex_amd_afc.h): its update kernel is part of libnavtex_amd.so, in a directory of
@@ -172,6 +177,10 @@ def _anc_jobs(hipcc: str, force: bool):
     return _companion_jobs(hipcc, force, ANC, [], ANC_HIP_SOURCES, ANC_CXX_SOURCES, also=(RESAMPLE,))
 
 
+def _notch_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, NOTCH, [], NOTCH_HIP_SOURCES, NOTCH_CXX_SOURCES, also=(RESAMPLE, DDC))
+
+
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
     # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
     tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
@@ -203,6 +212,8 @@ def build_lib(force: bool = False) -> Path:
     jobs += tap_jobs
     anc_objs, anc_jobs = _anc_jobs(hipcc, force)
     jobs += anc_jobs
+    notch_objs, notch_jobs = _notch_jobs(hipcc, force)
+    jobs += notch_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -246,6 +257,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, TAP_LIB, tap_objs, ["-lpthread", "-lm"])
     if force or _stale(ANC_LIB, anc_objs):
         _link(hipcc, ANC_LIB, anc_objs, ["-lpthread"])
+    if force or _stale(NOTCH_LIB, notch_objs):
+        _link(hipcc, NOTCH_LIB, notch_objs, ["-lpthread", "-lm"])
     return LIB
 
 
