@@ -24,54 +24,16 @@
 //       subtraction, two v_med3_i32 and a pack; 16-byte non-temporal stores where the output rows are 16-byte aligned.  The
 //       workgroup of a pair's last sample writes the other state row: the ring of the last W complete blocks, the open
 //       block's sums, the weight of the last sample, the coherence and reason of the last solve.
-// The formats' sizes, load_words, load_sample and the CF32 rule are the resampler's (nvx_rs_device.h).
-#include <type_traits>
-
+// The formats' sizes, load_words, load_sample and the CF32 rule are the resampler's (nvx_rs_device.h).  The step's shape, load
+// and store, the look-ahead rule, the wave sums, the 64-bit division and the dispatch on the format are the same-rate
+// companions' (nvx_stream_device.h).
 #include "nvx_anc_plan.h"
-#include "nvx_rs_device.h"
+#include "nvx_stream_device.h"
 
 static_assert(NVX_ANC_CS16 == NVX_RS_CS16 && NVX_ANC_CU8 == NVX_RS_CU8 && NVX_ANC_CS8 == NVX_RS_CS8 && NVX_ANC_CF32 == NVX_RS_CF32, "formats");
 
-typedef int64_t i64;
-typedef unsigned long long u64;
-
 // samples per lane and step, steps per region
-template <int FMT> struct Shape { static constexpr int SPT = (FMT == NVX_RS_CU8 || FMT == NVX_RS_CS8) ? 8 : 4, STEPS = NVX_ANC_REGION / (64 * SPT); };
-
-// step j of a thread's samples of the tile (`base` is its first sample of the tile, counted from the call's first) as packed
-// words; those behind the call's end are zero
-template <int FMT, bool FULL, bool NONTEMPORAL>
-__device__ __forceinline__ void load_step(const char *src, int base, int j, int n_in, uint32_t *w)
-{
-    constexpr int SPT = Shape<FMT>::SPT;
-    if (FULL || base + j * 64 * SPT + SPT <= n_in) load_words<FMT, NONTEMPORAL>(src, j * 64 * SPT, w);
-    else {
-#pragma unroll
-        for (int k = 0; k < SPT; k++) w[k] = base + j * 64 * SPT + k < n_in ? load_sample<FMT>(src, j * 64 * SPT + k) : 0u;
-    }
-}
-// float32 brings twice the bytes: a step is loaded when its turn comes, or sixty-four registers wait for the loads; the other
-// formats have a tile's loads in flight at once
-template <int FMT> struct Ahead { static constexpr bool value = FMT != NVX_RS_CF32; };
-
-// DPP: lanes without a source, and rows masked out, receive `old`
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, false); }
-enum { ROW_SHR1 = 0x111, ROW_SHR2 = 0x112, ROW_SHR4 = 0x114, ROW_SHR8 = 0x118, ROW_BCAST15 = 0x142, ROW_BCAST31 = 0x143 };
-
-// the wave's sum, uniform
-__device__ __forceinline__ int wave_sum(int v)
-{
-    v += dpp<ROW_SHR1, 0xf>(0, v); v += dpp<ROW_SHR2, 0xf>(0, v); v += dpp<ROW_SHR4, 0xf>(0, v); v += dpp<ROW_SHR8, 0xf>(0, v);
-    v += dpp<ROW_BCAST15, 0xa>(0, v); v += dpp<ROW_BCAST31, 0xc>(0, v);
-    return __builtin_amdgcn_readlane(v, 63);
-}
-// ... of 64-bit values, in three limbs of 22, 22 and 20 bits, whose sums over 64 lanes stay inside 32 bits
-__device__ __forceinline__ i64 wave_sum64(i64 v)
-{
-    const int l0 = (int)((uint32_t)v & 0x3fffffu), l1 = (int)((uint32_t)(v >> 22) & 0x3fffffu), l2 = (int)(v >> 44);
-    return (i64)wave_sum(l0) + ((i64)wave_sum(l1) << 22) + (i64)wave_sum(l2) * ((i64)1 << 44);
-}
+template <int FMT> using Shape = StreamShape<FMT, NVX_ANC_REGION>;
 
 // ------------------------------------------------------------------------------------------------------------------ sums
 struct Sums { u64 saa, sbb; i64 sre, sim; };
@@ -192,19 +154,6 @@ __global__ __launch_bounds__(NVX_ANC_THREADS) __attribute__((amdgpu_waves_per_eu
 }
 
 // ----------------------------------------------------------------------------------------------------------------- solve
-// n / d for d > 0, by shifts and subtractions: the compiler's 64-bit division goes through float32 reciprocals
-__device__ __forceinline__ u64 udiv64(u64 n, u64 d)
-{
-    u64 q = 0, r = 0;
-#pragma unroll 1
-    for (int b = 63; b >= 0; b--) {
-        r = (r << 1) | ((n >> b) & 1);
-        if (r >= d) { r -= d; q |= (u64)1 << b; }
-    }
-    return q;
-}
-__device__ __forceinline__ i64 floor_div(i64 n, i64 d) { return n >= 0 ? (i64)udiv64((u64)n, (u64)d) : -(i64)udiv64((u64)(-n) + (u64)d - 1, (u64)d); }
-
 // steps 1 .. 6 of the contract on the window's sums; returns the reason
 __device__ int solve(const i64 (&t)[NVX_ANC_SUMS], int window_log2, int &c_re, int &c_im, int &coherence)
 {
@@ -277,10 +226,7 @@ __global__ __launch_bounds__(NVX_ANC_THREADS) void nvx_anc_apply(const nvx_anc_a
             for (int k = 0; k < NVX_ANC_SUMS; k++) {
                 // the sums are uniform: through vector registers, or the whole solve is scalar code and its registers are
                 // spilled around every tile
-                const i64 sum = wave_sum64(lane < W ? record(r - W + lane, k) : 0);
-                int lo = (int)sum, hi = (int)(sum >> 32);
-                asm volatile("" : "+v"(lo), "+v"(hi));
-                t[k] = ((i64)hi << 32) | (uint32_t)lo;
+                t[k] = in_vector_registers(wave_sum64(lane < W ? record(r - W + lane, k) : 0));
             }
             if (lane == 0) {
                 int c_re, c_im, coh;
@@ -338,17 +284,7 @@ __global__ __launch_bounds__(NVX_ANC_THREADS) void nvx_anc_apply(const nvx_anc_a
 #pragma unroll
                 for (int k = 0; k < SPT; k++) wa[j * SPT + k] = cancel(wa[j * SPT + k], wb[j * SPT + k], c);
             }
-            if (a.out_vec && (FULL || base + j * 64 * SPT + SPT <= n_in)) {
-#pragma unroll
-                for (int k = 0; k < SPT; k += 4) {
-                    const u32x4 v = { wa[j * SPT + k], wa[j * SPT + k + 1], wa[j * SPT + k + 2], wa[j * SPT + k + 3] };
-                    __builtin_nontemporal_store(v, (u32x4 *)&dst[j * 64 * SPT + k]);
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < SPT; k++)
-                    if (FULL || base + j * 64 * SPT + k < n_in) dst[j * 64 * SPT + k] = wa[j * SPT + k];
-            }
+            store_step<FMT, FULL>(dst, a.out_vec, base, j, n_in, &wa[j * SPT]);
             __builtin_amdgcn_sched_barrier(0);
         }
     };
@@ -402,11 +338,5 @@ static hipError_t launch_both(const nvx_anc_args *a, dim3 grid, hipStream_t s)
 hipError_t nvx_anc_launch(const nvx_anc_args *a, int format, int n_pairs, int chunks, hipStream_t s)
 {
     const dim3 grid((unsigned)chunks, (unsigned)n_pairs);
-    switch (format) {
-    case NVX_ANC_CS16: return launch_both<NVX_RS_CS16>(a, grid, s);
-    case NVX_ANC_CU8:  return launch_both<NVX_RS_CU8>(a, grid, s);
-    case NVX_ANC_CS8:  return launch_both<NVX_RS_CS8>(a, grid, s);
-    case NVX_ANC_CF32: return launch_both<NVX_RS_CF32>(a, grid, s);
-    }
-    return hipErrorInvalidValue;
+    return nvx_for_format(format, [&](auto fmt) { return launch_both<decltype(fmt)::value>(a, grid, s); });
 }

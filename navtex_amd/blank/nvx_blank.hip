@@ -25,33 +25,19 @@
 // from nothing, storing and counting nothing: eight block ends later the ring, the partial sum and the detections of the
 // last block (hold reaches no further) are the stream's own.  The last chunk writes the other state row.
 // Integers only, except CF32's conversion.  The formats' sizes, load_sample and the CF32 rule are the resampler's
-// (nvx_rs_device.h), and so are the tile's 16-byte loads (load_words).  Registers: DESIGN 3.9 says why the A-part bounds
-// pass through an empty asm, why the detections are bits, and why a wave's own values come back from the LDS.
-#include <type_traits>
-
+// (nvx_rs_device.h), and so are the tile's 16-byte loads (load_words).  The step's shape and store, the DPP controls, the wave
+// sum and the dispatch on the format are the same-rate companions' (nvx_stream_device.h); the step's load is load_step's
+// body written out ("What the same-rate kernels share", says why).  Registers: DESIGN 3.9 says why the A-part bounds pass through an empty asm, why
+// the detections are bits, and why a wave's own values come back from the LDS.
 #include "nvx_blank_plan.h"
-#include "nvx_rs_device.h"
+#include "nvx_stream_device.h"
 
 static_assert(NVX_BLANK_CS16 == NVX_RS_CS16 && NVX_BLANK_CU8 == NVX_RS_CU8 && NVX_BLANK_CS8 == NVX_RS_CS8 && NVX_BLANK_CF32 == NVX_RS_CF32, "formats");
 
 #define NVX_BLANK_NONE (-(1 << 29))          // "no detection": further back than any hold, and far from wrapping
 #define NVX_BLANK_OFF 0xffffffffu            // a level no magnitude exceeds
 
-// DPP: lanes without a source, and rows masked out, receive `old`
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, false); }
-enum { ROW_SHR1 = 0x111, ROW_SHR2 = 0x112, ROW_SHR4 = 0x114, ROW_SHR8 = 0x118, WAVE_SHR1 = 0x138, ROW_BCAST15 = 0x142, ROW_BCAST31 = 0x143 };
-
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
-
-// the wave's sum, uniform
-__device__ __forceinline__ uint32_t wave_sum(uint32_t x)
-{
-    int v = (int)x;
-    v += dpp<ROW_SHR1, 0xf>(0, v); v += dpp<ROW_SHR2, 0xf>(0, v); v += dpp<ROW_SHR4, 0xf>(0, v); v += dpp<ROW_SHR8, 0xf>(0, v);
-    v += dpp<ROW_BCAST15, 0xa>(0, v); v += dpp<ROW_BCAST31, 0xc>(0, v);
-    return (uint32_t)__builtin_amdgcn_readlane(v, 63);
-}
 
 // the maximum over the lanes in front of this one (NVX_BLANK_NONE for lane 0); total: over the whole wave, uniform
 __device__ __forceinline__ int wave_max_before(int v, int &total)
@@ -77,8 +63,8 @@ __device__ __forceinline__ uint32_t level_of(const uint32_t (&s)[4], uint32_t co
     return (complete < 4 || thr_q8 == 0) ? NVX_BLANK_OFF : (lv > floor ? lv : floor);
 }
 
-// samples per lane and step, steps per region
-template <int FMT> struct Shape { static constexpr int SPT = (FMT == NVX_RS_CU8 || FMT == NVX_RS_CS8) ? 8 : 4, STEPS = NVX_BLANK_BLOCK / (64 * SPT); };
+// samples per lane and step, steps per region: a wave's region is a block
+template <int FMT> using Shape = StreamShape<FMT, NVX_BLANK_BLOCK>;
 
 template <int FMT>
 __global__ __launch_bounds__(NVX_BLANK_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void nvx_blank(const nvx_blank_args a)
@@ -215,17 +201,7 @@ __global__ __launch_bounds__(NVX_BLANK_THREADS) __attribute__((amdgpu_waves_per_
             front = imax(front, step_total[j] + step0 + j * 64 * SPT);
             if (live) {
                 n_blank += gone;
-                if (a.out_vec && (FULL || base + j * 64 * SPT + SPT <= n_in)) {
-#pragma unroll
-                    for (int k = 0; k < SPT; k += 4) {
-                        const u32x4 v = { w[j * SPT + k], w[j * SPT + k + 1], w[j * SPT + k + 2], w[j * SPT + k + 3] };
-                        __builtin_nontemporal_store(v, (u32x4 *)&dst[j * 64 * SPT + k]);
-                    }
-                } else {
-#pragma unroll
-                    for (int k = 0; k < SPT; k++)
-                        if (FULL || base + j * 64 * SPT + k < n_in) dst[j * 64 * SPT + k] = w[j * SPT + k];
-                }
+                store_step<FMT, FULL>(dst, a.out_vec, base, j, n_in, &w[j * SPT]);
             }
         }
         // the next tile counts its samples from its own first; the next call from the end of this one
@@ -257,11 +233,5 @@ static hipError_t launch_one(const nvx_blank_args *a, dim3 grid, hipStream_t s)
 hipError_t nvx_blank_launch(const nvx_blank_args *a, int format, int n_streams, int chunks, hipStream_t s)
 {
     const dim3 grid((unsigned)chunks, (unsigned)n_streams);
-    switch (format) {
-    case NVX_BLANK_CS16: return launch_one<NVX_RS_CS16>(a, grid, s);
-    case NVX_BLANK_CU8:  return launch_one<NVX_RS_CU8>(a, grid, s);
-    case NVX_BLANK_CS8:  return launch_one<NVX_RS_CS8>(a, grid, s);
-    case NVX_BLANK_CF32: return launch_one<NVX_RS_CF32>(a, grid, s);
-    }
-    return hipErrorInvalidValue;
+    return nvx_for_format(format, [&](auto fmt) { return launch_one<decltype(fmt)::value>(a, grid, s); });
 }

@@ -50,17 +50,18 @@ DDC_HIP_SOURCES = ["nvx_ddc.hip"]
 DDC_CXX_SOURCES = ["nvx_ddc_host.cpp"]
 DDC_SHARED_C_SOURCES = ["nvx_resample_design.c"]           # of RESAMPLE
 # the fourth companion (include/navtex_amd_blank.h): its own sources; its kernel includes the resampler's nvx_rs_device.h for
-# the formats' loads and conversions, and links nothing of it
+# the formats' loads and conversions, through nvx_stream_device.h beside it (the same-rate companions' streaming helpers),
+# and links nothing of either
 BLANK = PKG / "blank"
 BLANK_LIB = PKG / "libnavtex_amd_blank.so"
 BLANK_HIP_SOURCES = ["nvx_blank.hip"]
 BLANK_CXX_SOURCES = ["nvx_blank_host.cpp"]
-# the fifth companion (include/navtex_amd_iqc.h), built as the fourth is: nvx_rs_device.h again, and nothing linked
+# the fifth companion (include/navtex_amd_iqc.h), built as the fourth is: nvx_stream_device.h again, and nothing linked
 IQC = PKG / "iqc"
 IQC_LIB = PKG / "libnavtex_amd_iqc.so"
 IQC_HIP_SOURCES = ["nvx_iqc.hip"]
 IQC_CXX_SOURCES = ["nvx_iqc_host.cpp"]
-# the sixth companion (include/navtex_amd_real.h), built as the fourth and fifth are
+# the sixth companion (include/navtex_amd_real.h), built as the fourth and fifth are, on the same two headers
 REAL = PKG / "real"
 REAL_LIB = PKG / "libnavtex_amd_real.so"
 REAL_HIP_SOURCES = ["nvx_real.hip"]
@@ -77,12 +78,13 @@ TAP_LIB = PKG / "libnavtex_amd_tap.so"
 TAP_C_SOURCES = ["nvx_tap_design.c"]
 TAP_HIP_SOURCES = ["nvx_tap.hip"]
 TAP_CXX_SOURCES = ["nvx_tap_host.cpp"]
-# the antenna noise canceller (include/navtex_amd_anc.h), built as the fifth is: nvx_rs_device.h, and nothing linked
+# the antenna noise canceller (include/navtex_amd_anc.h), built as the fifth is: nvx_stream_device.h, and nothing linked
 ANC = PKG / "anc"
 ANC_LIB = PKG / "libnavtex_amd_anc.so"
 ANC_HIP_SOURCES = ["nvx_anc.hip"]
 ANC_CXX_SOURCES = ["nvx_anc_host.cpp"]
-# the tone notch (include/navtex_amd_notch.h), built as the canceller is; it also reads the bank's table header nvx_ddc_table.h
+# the tone notch (include/navtex_amd_notch.h), built as the canceller is, nvx_stream_device.h included; it also reads the bank's
+# table header nvx_ddc_table.h
 NOTCH = PKG / "notch"
 NOTCH_LIB = PKG / "libnavtex_amd_notch.so"
 NOTCH_HIP_SOURCES = ["nvx_notch.hip"]

@@ -24,21 +24,18 @@
 //       amplitude, the table word at the phase of that sample, e in 64 bits (a c reaches 2^35 at the rails), the rounding
 //       shift, the sum over the enabled notches, v_med3 clamps and a pack; 16-byte non-temporal stores where the output rows
 //       are 16-byte aligned.  The workgroup of a row's last sample writes the new delay line into the other state row.
-// The formats' sizes, load_words, load_sample and the CF32 rule are the resampler's (nvx_rs_device.h).
+// The formats' sizes, load_words, load_sample and the CF32 rule are the resampler's (nvx_rs_device.h).  The step's shape,
+// the wave sums in the last lane, in_vector_registers and the dispatch on the format are the same-rate companions'
+// (nvx_stream_device.h); the group load stays here, for its clamped-index tail.
 #include "nvx_notch_plan.h"
-#include "nvx_rs_device.h"
+#include "nvx_stream_device.h"
 
 static_assert(NVX_NOTCH_CS16 == NVX_RS_CS16 && NVX_NOTCH_CU8 == NVX_RS_CU8 && NVX_NOTCH_CS8 == NVX_RS_CS8 && NVX_NOTCH_CF32 == NVX_RS_CF32, "formats");
 
-typedef int64_t i64;
-typedef unsigned long long u64;
 typedef i64 i64x2 __attribute__((ext_vector_type(2)));
 
 // samples per lane and step, samples of a wave's step, steps per region, and the blocks a step can reach behind its first
-template <int FMT> struct Shape {
-    static constexpr int SPT = (FMT == NVX_RS_CU8 || FMT == NVX_RS_CS8) ? 8 : 4, STEP = 64 * SPT, STEPS = NVX_NOTCH_REGION / STEP,
-                         REACH = STEP / NVX_NOTCH_BLOCK;
-};
+template <int FMT> struct Shape : StreamShape<FMT, NVX_NOTCH_REGION> { static constexpr int REACH = Shape::STEP / NVX_NOTCH_BLOCK; };
 
 // the table, from the host's copy to the LDS: four 16-byte words per thread
 __device__ __forceinline__ void fill_table(uint32_t *tab, const uint32_t *src, int tid)
@@ -64,32 +61,6 @@ __device__ __forceinline__ void load_group_words(const char *row_src, int first,
             w[k] = base + k < n_in ? v : 0u;
         }
     }
-}
-
-// DPP: lanes without a source, and rows masked out, receive `old`.  The wave sums follow the noise canceller's (nvx_anc.hip).
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp(int old, int v) { return __builtin_amdgcn_update_dpp(old, v, CTRL, ROW_MASK, 0xf, false); }
-enum { ROW_SHR1 = 0x111, ROW_SHR2 = 0x112, ROW_SHR4 = 0x114, ROW_SHR8 = 0x118, ROW_BCAST15 = 0x142, ROW_BCAST31 = 0x143 };
-
-// the wave's sum, in lane 63: the sums stay in vector registers, which the sums kernels have to spare (their scalar ones are few)
-__device__ __forceinline__ int wave_sum_in_last_lane(int v)
-{
-    v += dpp<ROW_SHR1, 0xf>(0, v); v += dpp<ROW_SHR2, 0xf>(0, v); v += dpp<ROW_SHR4, 0xf>(0, v); v += dpp<ROW_SHR8, 0xf>(0, v);
-    v += dpp<ROW_BCAST15, 0xa>(0, v); v += dpp<ROW_BCAST31, 0xc>(0, v);
-    return v;
-}
-// ... of 64-bit values, in three limbs of 22, 22 and 20 bits, whose sums over 64 lanes stay inside 32 bits
-__device__ __forceinline__ i64 wave_sum64_in_last_lane(i64 v)
-{
-    const int l0 = (int)((uint32_t)v & 0x3fffffu), l1 = (int)((uint32_t)(v >> 22) & 0x3fffffu), l2 = (int)(v >> 44);
-    return (i64)wave_sum_in_last_lane(l0) + ((i64)wave_sum_in_last_lane(l1) << 22) + (i64)wave_sum_in_last_lane(l2) * ((i64)1 << 44);
-}
-
-__device__ __forceinline__ i64 in_vector_registers(i64 v)
-{
-    int lo = (int)v, hi = (int)(v >> 32);
-    asm volatile("" : "+v"(lo), "+v"(hi));
-    return ((i64)hi << 32) | (uint32_t)lo;
 }
 
 // ------------------------------------------------------------------------------------------------------------------ sums
@@ -348,11 +319,5 @@ static hipError_t launch_all(const nvx_notch_args *a, dim3 grid, hipStream_t s)
 hipError_t nvx_notch_launch(const nvx_notch_args *a, int format, int n_rows, int chunks, hipStream_t s)
 {
     const dim3 grid((unsigned)chunks, (unsigned)n_rows);
-    switch (format) {
-    case NVX_NOTCH_CS16: return launch_all<NVX_RS_CS16>(a, grid, s);
-    case NVX_NOTCH_CU8:  return launch_all<NVX_RS_CU8>(a, grid, s);
-    case NVX_NOTCH_CS8:  return launch_all<NVX_RS_CS8>(a, grid, s);
-    case NVX_NOTCH_CF32: return launch_all<NVX_RS_CF32>(a, grid, s);
-    }
-    return hipErrorInvalidValue;
+    return nvx_for_format(format, [&](auto fmt) { return launch_all<decltype(fmt)::value>(a, grid, s); });
 }

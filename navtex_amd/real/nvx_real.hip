@@ -25,32 +25,16 @@
 //            the call's end cuts.                                                                          -- barrier 2
 // The workgroup of a stream's last sample writes the other state row: the last 28 pairs of the stream, from the input, or
 // from the state row read where the call is shorter than that.
-// Integers only, except F32's conversion.
-#include <type_traits>
-
+// Integers only, except F32's conversion.  The step's shape and load, the look-ahead rule and the dispatch on the format are
+// the same-rate companions' (nvx_stream_device.h), which brings nvx_rs_device.h along.
 #include "nvx_real_plan.h"
-#include "nvx_rs_device.h"
+#include "nvx_stream_device.h"
 
 static_assert(NVX_REAL_S16 == NVX_RS_CS16 && NVX_REAL_U8 == NVX_RS_CU8 && NVX_REAL_S8 == NVX_RS_CS8 && NVX_REAL_F32 == NVX_RS_CF32, "formats");
 static_assert(NVX_REAL_HISTORY == 28 && NVX_REAL_HISTORY <= NVX_REAL_HALO_AT && NVX_REAL_HALO_AT % 8 == 0, "the halo");
 
-// pairs per lane and step, steps per region
-template <int FMT> struct Shape { static constexpr int SPT = (FMT == NVX_RS_CU8 || FMT == NVX_RS_CS8) ? 8 : 4, STEPS = NVX_REAL_REGION / (64 * SPT); };
-
-// step j of a thread's pairs of the tile (`base` is its first pair of the tile, counted from the call's first) as packed
-// words; those behind the call's end are zero
-template <int FMT, bool FULL>
-__device__ __forceinline__ void load_step(const char *src, int base, int j, int n, uint32_t *w)
-{
-    constexpr int SPT = Shape<FMT>::SPT;
-    if (FULL || base + j * 64 * SPT + SPT <= n) load_words<FMT, true>(src, j * 64 * SPT, w);
-    else {
-#pragma unroll
-        for (int k = 0; k < SPT; k++) w[k] = base + j * 64 * SPT + k < n ? load_sample<FMT>(src, j * 64 * SPT + k) : 0u;
-    }
-}
-// float32 brings twice the bytes: a step is loaded when its turn comes; the other formats have a tile's loads in flight at once
-template <int FMT> struct Ahead { static constexpr bool value = FMT != NVX_RS_CF32; };
+// pairs per lane and step, steps per region: a pair is what a sample is to the other companions
+template <int FMT> using Shape = StreamShape<FMT, NVX_REAL_REGION>;
 
 // element t of the row over o[m - 27 + t]: A[13] .. A[0], -A[0] .. -A[13]
 constexpr int tap_row(int t) { return t < NVX_REAL_NTAPS ? NVX_REAL_TAPS[NVX_REAL_K - t] : -NVX_REAL_TAPS[t - NVX_REAL_NTAPS]; }
@@ -94,7 +78,7 @@ __global__ __launch_bounds__(NVX_REAL_THREADS) void nvx_real(const nvx_real_args
         uint32_t w[16];
         if constexpr (Ahead<FMT>::value) {
 #pragma unroll
-            for (int j = 0; j < STEPS; j++) load_step<FMT, FULL>(src, base, j, n, &w[j * SPT]);
+            for (int j = 0; j < STEPS; j++) load_step<FMT, FULL, true>(src, base, j, n, &w[j * SPT]);
         }
         if (tid < NVX_REAL_HISTORY) {
             const uint32_t h = tbase == 0 ? st[tid] : load_sample<FMT>(row, tbase - NVX_REAL_HISTORY + tid);
@@ -103,7 +87,7 @@ __global__ __launch_bounds__(NVX_REAL_THREADS) void nvx_real(const nvx_real_args
         }
 #pragma unroll
         for (int j = 0; j < STEPS; j++) {
-            if constexpr (!Ahead<FMT>::value) load_step<FMT, FULL>(src, base, j, n, &w[j * SPT]);
+            if constexpr (!Ahead<FMT>::value) load_step<FMT, FULL, true>(src, base, j, n, &w[j * SPT]);
             const int at = NVX_REAL_HALO_AT + first + j * 64 * SPT;
             stage_t e, o;
             const uint32_t *const p = &w[j * SPT];
@@ -177,11 +161,5 @@ static hipError_t launch_one(const nvx_real_args *a, dim3 grid, hipStream_t s)
 hipError_t nvx_real_launch(const nvx_real_args *a, int format, int n_streams, int chunks, hipStream_t s)
 {
     const dim3 grid((unsigned)chunks, (unsigned)n_streams);
-    switch (format) {
-    case NVX_REAL_S16: return launch_one<NVX_RS_CS16>(a, grid, s);
-    case NVX_REAL_U8:  return launch_one<NVX_RS_CU8>(a, grid, s);
-    case NVX_REAL_S8:  return launch_one<NVX_RS_CS8>(a, grid, s);
-    case NVX_REAL_F32: return launch_one<NVX_RS_CF32>(a, grid, s);
-    }
-    return hipErrorInvalidValue;
+    return nvx_for_format(format, [&](auto fmt) { return launch_one<decltype(fmt)::value>(a, grid, s); });
 }

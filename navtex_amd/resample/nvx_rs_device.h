@@ -1,8 +1,10 @@
 // nvx_rs_device.h -- what the kernels of the resampler (nvx_resample.hip), of the down-converter bank
-// (navtex_amd/ddc/nvx_ddc.hip), of the blanker (navtex_amd/blank/nvx_blank.hip) and of the IQ corrector
-// (navtex_amd/iqc/nvx_iqc.hip) have word for word in common: the vector types, the small arithmetic, the formats'
-// conversions, and the launch of a kernel family's eight instances.  Internal; each library compiles its own copy.  The
-// kernel bodies stay in their files: see DESIGN 3.8.
+// (navtex_amd/ddc/nvx_ddc.hip), of the narrowband interpolator, of the channel tap and of the same-rate companions have
+// word for word in common: the vector types, the small arithmetic, the formats' conversions, and the launch of a kernel
+// family's eight instances.  The same-rate companions (blanker, IQ corrector, real-input converter, noise canceller, tone
+// notch) include it through nvx_stream_device.h, which adds their streaming helpers: the step's shape, load and store, the
+// wave sums, the 64-bit division, the dispatch on the format.  Internal; each library compiles its own copy.  The kernel
+// bodies stay in their files: see DESIGN 3.8.
 #ifndef NVX_RS_DEVICE_H
 #define NVX_RS_DEVICE_H
 

@@ -8,12 +8,13 @@ the instruction streams of the kernels whose demangled names match in both (labe
 every device translation unit of libnavtex_amd.so (navtex_amd/csrc/*.hip), of the scan library (navtex_amd/scan/*.hip), of
 the resampler (navtex_amd/resample/*.hip), of the down-converter bank (navtex_amd/ddc/*.hip), of the blanker
 (navtex_amd/blank/*.hip), of the IQ corrector (navtex_amd/iqc/*.hip), of the real-input converter (navtex_amd/real/*.hip), of
-the narrowband interpolator (navtex_amd/narrow/*.hip), of the channel tap (navtex_amd/tap/*.hip) and of the noise canceller
-(navtex_amd/anc/*.hip; all with the resampler's and the bank's directories on their include path), each where the revision has
-it.  That is how a feature that lives in a library of its own shows that it left
+the narrowband interpolator (navtex_amd/narrow/*.hip), of the channel tap (navtex_amd/tap/*.hip), of the noise canceller
+(navtex_amd/anc/*.hip) and of the tone notch (navtex_amd/notch/*.hip; all with the resampler's and the bank's directories on
+their include path), each where the revision has it.  That is how a feature that lives in a library of its own shows that it left
 the other kernels alone (profiles/resample_isa_identical.txt, profiles/ddc_isa_identical.txt,
 profiles/blank_isa_identical.txt, profiles/iqc_isa_identical.txt, profiles/real_isa_identical.txt), and how
-a change that moves code between these files shows that no kernel changed (profiles/rs_shared_isa_identical.txt).  Used in
+a change that moves code between these files shows that no kernel changed (profiles/rs_shared_isa_identical.txt,
+profiles/stream_device_isa_identical.txt).  Used in
 round 5 to show that pruning the A/B alternates out of the roofline kernel changed no instruction of the kernels that
 ship (profiles/r05/a0_prune_isa_identical.txt); hipcc cross-compiles, no GPU needed."""
 import re
@@ -24,7 +25,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 COMPANIONS = ("navtex_amd/scan", "navtex_amd/resample", "navtex_amd/ddc", "navtex_amd/blank", "navtex_amd/iqc", "navtex_amd/real",
-              "navtex_amd/narrow", "navtex_amd/tap", "navtex_amd/anc")
+              "navtex_amd/narrow", "navtex_amd/tap", "navtex_amd/anc", "navtex_amd/notch")
 
 
 def compile_tree(tree: Path, out: Path, everything: bool = False) -> dict:
