@@ -11,7 +11,7 @@
  * shift, on the mirrored output frequency: a station at +d has its image at -d, and the filter's stop band is the only thing
  * that removes it.  The library has no notion of rate: everything below is in samples.  To feed the
  * down-converter bank or the resampler (navtex_amd_ddc.h, navtex_amd_resample.h: 96 kS/s .. 3.2 MS/s) fr is 192 kS/s ..
- * 6.4 MS/s.
+ * 6.4 MS/s; a faster ADC's IQ goes through the zoom bank first (navtex_amd_zoom.h).
  *
  * THE ARITHMETIC, operation by operation.  Integer arithmetic except the one float32 conversion of F32 input.  The GPU
  * result equals a restatement of this text word for word (==, no tolerance).

@@ -4,7 +4,8 @@ navtex_amd/resample/), libnavtex_amd_ddc.so (the down-converter bank, navtex_amd
 impulse noise blanker, navtex_amd/blank/), libnavtex_amd_iqc.so (the IQ corrector, navtex_amd/iqc/), libnavtex_amd_real.so
 (the real-input converter, navtex_amd/real/), libnavtex_amd_narrow.so (the narrowband interpolator, navtex_amd/narrow/),
 libnavtex_amd_tap.so (the channel tap, navtex_amd/tap/), libnavtex_amd_anc.so (the antenna noise canceller,
-navtex_amd/anc/) and libnavtex_amd_notch.so (the tone notch, navtex_amd/notch/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
+navtex_amd/anc/), libnavtex_amd_notch.so (the tone notch, navtex_amd/notch/) and libnavtex_amd_zoom.so (the zoom bank,
+navtex_amd/zoom/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
 reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
@@ -89,6 +90,12 @@ NOTCH = PKG / "notch"
 NOTCH_LIB = PKG / "libnavtex_amd_notch.so"
 NOTCH_HIP_SOURCES = ["nvx_notch.hip"]
 NOTCH_CXX_SOURCES = ["nvx_notch_host.cpp"]
+# the zoom bank (include/navtex_amd_zoom.h), built as the notch is; it reads the bank's table header nvx_ddc_table.h and the
+# real-input converter's taps nvx_real_taps.h
+ZOOM = PKG / "zoom"
+ZOOM_LIB = PKG / "libnavtex_amd_zoom.so"
+ZOOM_HIP_SOURCES = ["nvx_zoom.hip"]
+ZOOM_CXX_SOURCES = ["nvx_zoom_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp", "nvx_afc.cpp"]
 # automatic frequency control (include/navtex_amd_afc.h): its update kernel is part of libnavtex_amd.so, in a directory of
@@ -183,6 +190,10 @@ def _notch_jobs(hipcc: str, force: bool):
     return _companion_jobs(hipcc, force, NOTCH, [], NOTCH_HIP_SOURCES, NOTCH_CXX_SOURCES, also=(RESAMPLE, DDC))
 
 
+def _zoom_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, ZOOM, [], ZOOM_HIP_SOURCES, ZOOM_CXX_SOURCES, also=(RESAMPLE, DDC, REAL))
+
+
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
     # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
     tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
@@ -216,6 +227,8 @@ def build_lib(force: bool = False) -> Path:
     jobs += anc_jobs
     notch_objs, notch_jobs = _notch_jobs(hipcc, force)
     jobs += notch_jobs
+    zoom_objs, zoom_jobs = _zoom_jobs(hipcc, force)
+    jobs += zoom_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -261,6 +274,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, ANC_LIB, anc_objs, ["-lpthread"])
     if force or _stale(NOTCH_LIB, notch_objs):
         _link(hipcc, NOTCH_LIB, notch_objs, ["-lpthread", "-lm"])
+    if force or _stale(ZOOM_LIB, zoom_objs):
+        _link(hipcc, ZOOM_LIB, zoom_objs, ["-lpthread", "-lm"])
     return LIB
 
 

@@ -9,10 +9,11 @@ every device translation unit of libnavtex_amd.so (navtex_amd/csrc/*.hip), of th
 the resampler (navtex_amd/resample/*.hip), of the down-converter bank (navtex_amd/ddc/*.hip), of the blanker
 (navtex_amd/blank/*.hip), of the IQ corrector (navtex_amd/iqc/*.hip), of the real-input converter (navtex_amd/real/*.hip), of
 the narrowband interpolator (navtex_amd/narrow/*.hip), of the channel tap (navtex_amd/tap/*.hip), of the noise canceller
-(navtex_amd/anc/*.hip) and of the tone notch (navtex_amd/notch/*.hip; all with the resampler's and the bank's directories on
-their include path), each where the revision has it.  That is how a feature that lives in a library of its own shows that it left
+(navtex_amd/anc/*.hip), of the tone notch (navtex_amd/notch/*.hip) and of the zoom bank (navtex_amd/zoom/*.hip; all with the
+resampler's, the bank's and the converter's directories on their include path), each where the revision has it.  That is how a feature that lives in a library of its own shows that it left
 the other kernels alone (profiles/resample_isa_identical.txt, profiles/ddc_isa_identical.txt,
-profiles/blank_isa_identical.txt, profiles/iqc_isa_identical.txt, profiles/real_isa_identical.txt), and how
+profiles/blank_isa_identical.txt, profiles/iqc_isa_identical.txt, profiles/real_isa_identical.txt,
+profiles/zoom_isa_identical.txt), and how
 a change that moves code between these files shows that no kernel changed (profiles/rs_shared_isa_identical.txt,
 profiles/stream_device_isa_identical.txt).  Used in
 round 5 to show that pruning the A/B alternates out of the roofline kernel changed no instruction of the kernels that
@@ -25,7 +26,7 @@ from pathlib import Path
 
 ROOT = Path(__file__).resolve().parent.parent
 COMPANIONS = ("navtex_amd/scan", "navtex_amd/resample", "navtex_amd/ddc", "navtex_amd/blank", "navtex_amd/iqc", "navtex_amd/real",
-              "navtex_amd/narrow", "navtex_amd/tap", "navtex_amd/anc", "navtex_amd/notch")
+              "navtex_amd/narrow", "navtex_amd/tap", "navtex_amd/anc", "navtex_amd/notch", "navtex_amd/zoom")
 
 
 def compile_tree(tree: Path, out: Path, everything: bool = False) -> dict:
@@ -36,7 +37,7 @@ def compile_tree(tree: Path, out: Path, everything: bool = False) -> dict:
     text = ""
     for src in sources:
         subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17", f"-I{tree / 'include'}", f"-I{csrc}",
-                        f"-I{src.parent}", f"-I{tree / 'navtex_amd' / 'resample'}", f"-I{tree / 'navtex_amd' / 'ddc'}", "-cuid=same", "--cuda-device-only", "-S", str(src), "-o", str(out)], check=True, capture_output=True)
+                        f"-I{src.parent}", f"-I{tree / 'navtex_amd' / 'resample'}", f"-I{tree / 'navtex_amd' / 'ddc'}", f"-I{tree / 'navtex_amd' / 'real'}", "-cuid=same", "--cuda-device-only", "-S", str(src), "-o", str(out)], check=True, capture_output=True)
         text += out.read_text()
     kernels = {}
     for sym in re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, flags=re.M):         # the kernels, not the data symbols
