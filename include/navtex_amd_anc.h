@@ -59,7 +59,9 @@
  * Known limits.
  *   (a) It is one complex weight for the whole row.  Noise that reaches the two antennas with a delay difference tau is
  *       nulled to about 20 log10(2 pi f tau) at offset f from the row's centre.  For antennas a few tens of metres apart
- *       that is 30 dB or more at +-14 kHz.  A narrower row nulls deeper.
+ *       that is 30 dB or more at +-14 kHz.  A narrower row nulls deeper.  The two rows must be sample-aligned: rows that start
+ *       any number of samples apart (two dongles on one clock) go through the row aligner first (navtex_amd_align.h), which
+ *       measures the delay and removes it to 1/32 sample.
  *   (b) It is blind: it cancels the strongest component the two rows share.  A station that is itself that component is
  *       taken down to about the level of the sense row's own noise (DESIGN 3.14 has figures).  NVX_ANC_HOLD and nvx_anc_set
  *       are for calibrated set-ups, and the coherence tells the caller which case it is in.

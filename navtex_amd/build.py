@@ -4,8 +4,8 @@ navtex_amd/resample/), libnavtex_amd_ddc.so (the down-converter bank, navtex_amd
 impulse noise blanker, navtex_amd/blank/), libnavtex_amd_iqc.so (the IQ corrector, navtex_amd/iqc/), libnavtex_amd_real.so
 (the real-input converter, navtex_amd/real/), libnavtex_amd_narrow.so (the narrowband interpolator, navtex_amd/narrow/),
 libnavtex_amd_tap.so (the channel tap, navtex_amd/tap/), libnavtex_amd_anc.so (the antenna noise canceller,
-navtex_amd/anc/), libnavtex_amd_notch.so (the tone notch, navtex_amd/notch/) and libnavtex_amd_zoom.so (the zoom bank,
-navtex_amd/zoom/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
+navtex_amd/anc/), libnavtex_amd_notch.so (the tone notch, navtex_amd/notch/), libnavtex_amd_zoom.so (the zoom bank,
+navtex_amd/zoom/) and libnavtex_amd_align.so (the row aligner, navtex_amd/align/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
 reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
@@ -96,6 +96,13 @@ ZOOM = PKG / "zoom"
 ZOOM_LIB = PKG / "libnavtex_amd_zoom.so"
 ZOOM_HIP_SOURCES = ["nvx_zoom.hip"]
 ZOOM_CXX_SOURCES = ["nvx_zoom_host.cpp"]
+# the row aligner (include/navtex_amd_align.h), built as the canceller is, nvx_stream_device.h included; its host-only parts
+# (the estimate, and the taps from csrc/nvx_polyphase_design.h) are plain C
+ALIGN = PKG / "align"
+ALIGN_LIB = PKG / "libnavtex_amd_align.so"
+ALIGN_C_SOURCES = ["nvx_align_find.c"]
+ALIGN_HIP_SOURCES = ["nvx_align.hip"]
+ALIGN_CXX_SOURCES = ["nvx_align_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp", "nvx_afc.cpp"]
 # automatic frequency control (include/navtex_amd_afc.h): its update kernel is part of libnavtex_amd.so, in a directory of
@@ -194,6 +201,10 @@ def _zoom_jobs(hipcc: str, force: bool):
     return _companion_jobs(hipcc, force, ZOOM, [], ZOOM_HIP_SOURCES, ZOOM_CXX_SOURCES, also=(RESAMPLE, DDC, REAL))
 
 
+def _align_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, ALIGN, ALIGN_C_SOURCES, ALIGN_HIP_SOURCES, ALIGN_CXX_SOURCES, also=(RESAMPLE,))
+
+
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
     # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
     tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
@@ -229,6 +240,8 @@ def build_lib(force: bool = False) -> Path:
     jobs += notch_jobs
     zoom_objs, zoom_jobs = _zoom_jobs(hipcc, force)
     jobs += zoom_jobs
+    align_objs, align_jobs = _align_jobs(hipcc, force)
+    jobs += align_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -276,6 +289,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, NOTCH_LIB, notch_objs, ["-lpthread", "-lm"])
     if force or _stale(ZOOM_LIB, zoom_objs):
         _link(hipcc, ZOOM_LIB, zoom_objs, ["-lpthread", "-lm"])
+    if force or _stale(ALIGN_LIB, align_objs):
+        _link(hipcc, ALIGN_LIB, align_objs, ["-lpthread", "-lm"])
     return LIB
 
 

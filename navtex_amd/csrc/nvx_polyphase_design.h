@@ -50,23 +50,31 @@ static inline int nvx_pp_even_taps(double per_phase)
     return t;
 }
 
-/* The prototype of L * T taps with its cut-off at fc cycles per sample, and behind it the T-entry row nvx_pp_phase fills:
- * one allocation, the caller's to free; NULL where there is no memory. */
-static inline double *nvx_pp_prototype(double fc, int L, int T, long long **row)
+/* The prototype of L * T taps with its cut-off at fc cycles per sample, centred on index `centre`, and behind it the T-entry
+ * row nvx_pp_phase fills: one allocation, the caller's to free; NULL where there is no memory.  The window is L * T wide
+ * around the centre whatever the centre is: centred on the whole index L * T / 2 (the row aligner's) the prototype is that of
+ * L * T + 1 taps whose last is zero, and phase 0 of a Nyquist cut-off is a unit tap. */
+static inline double *nvx_pp_prototype_at(double fc, int L, int T, double centre, long long **row)
 {
     const int nt = L * T;
     double *p = (double *)malloc((size_t)nt * sizeof(double) + (size_t)T * sizeof(long long));
     if (!p) return NULL;
     const double beta = 0.1102 * (NVX_PP_DESIGN_DB - 8.7);
-    const double centre = 0.5 * (nt - 1), i0b = nvx_pp_bessel_i0(beta);
+    const double half = 0.5 * nt, i0b = nvx_pp_bessel_i0(beta);
     for (int k = 0; k < nt; k++) {
-        const double d = k - centre, u = d / (centre + 0.5);     /* the window reaches zero half a sample beyond the ends */
+        const double d = k - centre, u = d / half;               /* the window reaches zero half the length from the centre */
         const double a = 2.0 * NVX_PP_PI * fc * d;
         const double sinc = fabs(a) < 1e-12 ? 1.0 : sin(a) / a;
         p[k] = 2.0 * fc * sinc * nvx_pp_bessel_i0(beta * sqrt(1.0 - u * u)) / i0b;
     }
     *row = (long long *)(p + nt);
     return p;
+}
+
+/* ... centred between its two middle taps: the rate changers' */
+static inline double *nvx_pp_prototype(double fc, int L, int T, long long **row)
+{
+    return nvx_pp_prototype_at(fc, L, T, 0.5 * (L * T - 1), row);
 }
 
 /* Phase r of the prototype, normalised to sum 1 and rounded at `shift`, into row[0 .. T); returns the row's sum and leaves
