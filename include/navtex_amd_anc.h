@@ -62,6 +62,8 @@
  *       that is 30 dB or more at +-14 kHz.  A narrower row nulls deeper.  The two rows must be sample-aligned: rows that start
  *       any number of samples apart (two dongles on one clock) go through the row aligner first (navtex_amd_align.h), which
  *       measures the delay and removes it to 1/32 sample.
+ *       Noise that arrives with echoes or over a frequency response wants more than one weight: the multi-tap canceller
+ *       (navtex_amd_wanc.h) puts a short complex FIR on the sense row.
  *   (b) It is blind: it cancels the strongest component the two rows share.  A station that is itself that component is
  *       taken down to about the level of the sense row's own noise (DESIGN 3.14 has figures).  NVX_ANC_HOLD and nvx_anc_set
  *       are for calibrated set-ups, and the coherence tells the caller which case it is in.
