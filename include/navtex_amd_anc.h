@@ -68,6 +68,8 @@
  *       taken down to about the level of the sense row's own noise (DESIGN 3.14 has figures).  NVX_ANC_HOLD and nvx_anc_set
  *       are for calibrated set-ups, and the coherence tells the caller which case it is in.
  *   (c) A DC offset on both rows is a common component.  Take it out first, which the IQ corrector does.
+ *   (d) It subtracts what the two rows share and cannot add it: a station that fades on two antennas at different times is
+ *       the diversity combiner's (navtex_amd_div.h), which co-phases the two rows per station and adds them.
  * Cost.  Both rows are read twice and 4 bytes written per sample (CS16: 20 bytes per pair-sample against the IQ corrector's
  *   12 per sample).
  *

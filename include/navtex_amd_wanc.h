@@ -84,6 +84,8 @@
  *   (d) A window in which the path changes solves to a compromise.
  *   (e) The matrix is the Toeplitz one of r[d]: the few products at a window's edges that a full covariance matrix would
  *       place differently are not told apart.
+ *   (f) It subtracts what the two rows share and cannot add it: a station that fades on two antennas at different times is
+ *       the diversity combiner's (navtex_amd_div.h), which co-phases the two rows per station and adds them.
  * Cost.  Both rows are read twice and 4 bytes written per sample, as in navtex_amd_anc.h; 4 K + 1 sums per sample in the
  *   first pass and 2 K dot products in the second.
  *

@@ -5,8 +5,8 @@ impulse noise blanker, navtex_amd/blank/), libnavtex_amd_iqc.so (the IQ correcto
 (the real-input converter, navtex_amd/real/), libnavtex_amd_narrow.so (the narrowband interpolator, navtex_amd/narrow/),
 libnavtex_amd_tap.so (the channel tap, navtex_amd/tap/), libnavtex_amd_anc.so (the antenna noise canceller,
 navtex_amd/anc/), libnavtex_amd_notch.so (the tone notch, navtex_amd/notch/), libnavtex_amd_zoom.so (the zoom bank,
-navtex_amd/zoom/), libnavtex_amd_align.so (the row aligner, navtex_amd/align/) and libnavtex_amd_wanc.so (the multi-tap noise
-canceller, navtex_amd/wanc/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
+navtex_amd/zoom/), libnavtex_amd_align.so (the row aligner, navtex_amd/align/), libnavtex_amd_wanc.so (the multi-tap noise
+canceller, navtex_amd/wanc/) and libnavtex_amd_div.so (the diversity combiner, navtex_amd/div/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
 reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
@@ -109,6 +109,12 @@ WANC = PKG / "wanc"
 WANC_LIB = PKG / "libnavtex_amd_wanc.so"
 WANC_HIP_SOURCES = ["nvx_wanc.hip"]
 WANC_CXX_SOURCES = ["nvx_wanc_host.cpp"]
+# the diversity combiner (include/navtex_amd_div.h), built as the notch is: nvx_stream_device.h and the bank's table header
+# nvx_ddc_table.h, and nothing linked
+DIV = PKG / "div"
+DIV_LIB = PKG / "libnavtex_amd_div.so"
+DIV_HIP_SOURCES = ["nvx_div.hip"]
+DIV_CXX_SOURCES = ["nvx_div_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp", "nvx_afc.cpp"]
 # automatic frequency control (include/navtex_amd_afc.h): its update kernel is part of libnavtex_amd.so, in a directory of
@@ -215,6 +221,10 @@ def _wanc_jobs(hipcc: str, force: bool):
     return _companion_jobs(hipcc, force, WANC, [], WANC_HIP_SOURCES, WANC_CXX_SOURCES, also=(RESAMPLE,))
 
 
+def _div_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, DIV, [], DIV_HIP_SOURCES, DIV_CXX_SOURCES, also=(RESAMPLE, DDC))
+
+
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
     # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
     tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
@@ -254,6 +264,8 @@ def build_lib(force: bool = False) -> Path:
     jobs += align_jobs
     wanc_objs, wanc_jobs = _wanc_jobs(hipcc, force)
     jobs += wanc_jobs
+    div_objs, div_jobs = _div_jobs(hipcc, force)
+    jobs += div_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -305,6 +317,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, ALIGN_LIB, align_objs, ["-lpthread", "-lm"])
     if force or _stale(WANC_LIB, wanc_objs):
         _link(hipcc, WANC_LIB, wanc_objs, ["-lpthread"])
+    if force or _stale(DIV_LIB, div_objs):
+        _link(hipcc, DIV_LIB, div_objs, ["-lpthread", "-lm"])
     return LIB
 
 

@@ -1,6 +1,6 @@
 // nvx_companion.h -- what the host sides of the companion libraries have in common.  For all of them: the thread's error
 // text, HIP_TRY, the device and span checks, HIP-event timing.  For those that carry rows of streams from call to call (the
-// blanker, the IQ corrector, the real-input converter, the noise canceller, the tone notch, the row aligner, the multi-tap noise canceller, and the rate changers: the resampler,
+// blanker, the IQ corrector, the real-input converter, the noise canceller, the tone notch, the row aligner, the multi-tap noise canceller, the diversity combiner, and the rate changers: the resampler,
 // the down-converter bank, the narrowband interpolator, the channel tap, the zoom bank), below those: the position and row checks, the state rows
 // read and written alternately, a push's staging buffers.  Internal, and all of it static: every library compiles its own
 // copy and they share no state.  The main library has nvx_handle.h instead.

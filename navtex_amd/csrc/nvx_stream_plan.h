@@ -1,5 +1,5 @@
 /* nvx_stream_plan.h -- the launch arithmetic the companions that carry rows of streams share (the blanker, the IQ corrector,
- * the real-input converter, the noise canceller, the zoom bank, the row aligner, the multi-tap noise canceller; the polyphase plan and the narrowband interpolator for the first
+ * the real-input converter, the noise canceller, the zoom bank, the row aligner, the multi-tap noise canceller, the diversity combiner; the polyphase plan and the narrowband interpolator for the first
  * two): how a
  * row's tiles are spread over workgroups, and when a launch may store 16 bytes at a time.  Pure C, no HIP: each library's
  * nvx_*_fill_args calls these with its own constants, and tests/harness/stream_plan_core.cpp walks them without a device.

@@ -5,7 +5,8 @@
 // call's first sample: the step's shape, its load and its store, the wave sums over DPP, the 64-bit division of the block
 // solves, and the host side's dispatch on the format.  The zoom bank (navtex_amd/zoom/nvx_zoom.hip) takes the lane's group and
 // the dispatch from here; the row aligner (navtex_amd/align/nvx_align.hip) the step's store, the wave sums and the dispatch; the multi-tap noise
-// canceller (navtex_amd/wanc/nvx_wanc.hip) the step's shape and load, the wave sums and the dispatch.  Internal; each library
+// canceller (navtex_amd/wanc/nvx_wanc.hip) the step's shape and load, the wave sums and the dispatch; the diversity combiner
+// (navtex_amd/div/nvx_div.hip) the step's shape, load and store, the wave sums, in_vector_registers and the dispatch.  Internal; each library
 // compiles its own copy and nothing is linked.
 // The kernel bodies stay in their files, and so does what a kernel compiles differently through a helper: the
 // blanker's step load, the converter's and the notch's one-group stores ("What the same-rate kernels share").
