@@ -6,7 +6,8 @@ impulse noise blanker, navtex_amd/blank/), libnavtex_amd_iqc.so (the IQ correcto
 libnavtex_amd_tap.so (the channel tap, navtex_amd/tap/), libnavtex_amd_anc.so (the antenna noise canceller,
 navtex_amd/anc/), libnavtex_amd_notch.so (the tone notch, navtex_amd/notch/), libnavtex_amd_zoom.so (the zoom bank,
 navtex_amd/zoom/), libnavtex_amd_align.so (the row aligner, navtex_amd/align/), libnavtex_amd_wanc.so (the multi-tap noise
-canceller, navtex_amd/wanc/) and libnavtex_amd_div.so (the diversity combiner, navtex_amd/div/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
+canceller, navtex_amd/wanc/), libnavtex_amd_div.so (the diversity combiner, navtex_amd/div/) and libnavtex_amd_spec.so (the
+spectrum monitor, navtex_amd/spec/) in-tree with hipcc, and -- for tests only -- the oracle library and the compiled
 reference seams via oracle/Makefile.
 
     python navtex_amd/build.py            # product library
@@ -115,6 +116,13 @@ DIV = PKG / "div"
 DIV_LIB = PKG / "libnavtex_amd_div.so"
 DIV_HIP_SOURCES = ["nvx_div.hip"]
 DIV_CXX_SOURCES = ["nvx_div_host.cpp"]
+# the spectrum monitor (include/navtex_amd_spec.h), built as the notch is: nvx_stream_device.h for the formats' loads, its own
+# generated table nvx_spec_table.h, a host-only finder in plain C, and nothing linked
+SPEC = PKG / "spec"
+SPEC_LIB = PKG / "libnavtex_amd_spec.so"
+SPEC_C_SOURCES = ["nvx_spec_find.c"]
+SPEC_HIP_SOURCES = ["nvx_spec.hip"]
+SPEC_CXX_SOURCES = ["nvx_spec_host.cpp"]
 CXX_SOURCES = ["nvx_api.cpp", "nvx_push.cpp", "nvx_shim.cpp", "nvx_capture.cpp", "nvx_wideband.cpp", "nvx_synth_dev.cpp", "nvx_fsm_host.cpp", "nvx_group.cpp",
                "nvx_tune.cpp", "nvx_afc.cpp"]
 # automatic frequency control (include/navtex_amd_afc.h): its update kernel is part of libnavtex_amd.so, in a directory of
@@ -225,6 +233,10 @@ def _div_jobs(hipcc: str, force: bool):
     return _companion_jobs(hipcc, force, DIV, [], DIV_HIP_SOURCES, DIV_CXX_SOURCES, also=(RESAMPLE, DDC))
 
 
+def _spec_jobs(hipcc: str, force: bool):
+    return _companion_jobs(hipcc, force, SPEC, SPEC_C_SOURCES, SPEC_HIP_SOURCES, SPEC_CXX_SOURCES, also=(RESAMPLE,))
+
+
 def _link(hipcc: str, lib: Path, objs, libs=()) -> None:
     # link beside the target and rename: another process (a second rank, a test runner) never maps a half-written file
     tmp = lib.with_name(lib.name + f".tmp{os.getpid()}")
@@ -266,6 +278,8 @@ def build_lib(force: bool = False) -> Path:
     jobs += wanc_jobs
     div_objs, div_jobs = _div_jobs(hipcc, force)
     jobs += div_jobs
+    spec_objs, spec_jobs = _spec_jobs(hipcc, force)
+    jobs += spec_jobs
     for src in C_SOURCES:
         o = OBJ / (src + ".o")
         if force or _stale(o, [CSRC / src] + headers):
@@ -319,6 +333,8 @@ def build_lib(force: bool = False) -> Path:
         _link(hipcc, WANC_LIB, wanc_objs, ["-lpthread"])
     if force or _stale(DIV_LIB, div_objs):
         _link(hipcc, DIV_LIB, div_objs, ["-lpthread", "-lm"])
+    if force or _stale(SPEC_LIB, spec_objs):
+        _link(hipcc, SPEC_LIB, spec_objs, ["-lpthread", "-lm"])
     return LIB
 
 
